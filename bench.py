@@ -12,6 +12,19 @@ Rank 0 prints ONE JSON line with the whole-job samples/sec.  (Under
 the production nccl/RCCL backend stdout carries only that line; the
 gloo TEST backend prints its own "[Gloo] Rank..." connectivity banners
 to stdout — pipe through `grep '^{'` when parsing gloo runs.)
+
+A plain run does only what the headline figure needs: set up, warm up,
+time the K steps, print the line.  `--dump-outputs DIR` additionally
+writes what the last timed step left behind (the updated f32 master
+parameters and the f32 gradients that produced them) as DIR/<name>.npy.
+The step runs whatever path the arguments select (split-K atomic wgrad
+unless `--deterministic` is given).  Data and initial weights are
+seeded, and a dump run starts its last timed step from the initial
+weights again, so that step's inputs are identical from run to run and
+two builds can be compared output for output: what remains between runs
+is the f32 summation order of one step's atomics (none at all under
+`--deterministic`).  `--full` is where any measurement beyond the
+headline figure belongs (there is none today).
 """
 
 import argparse
@@ -20,6 +33,46 @@ import os
 import time
 
 import torch
+
+# --dump-outputs cap: 64 MB of float32 in all
+_DUMP_BUDGET_ELEMS = (64 << 20) // 4
+
+
+def sample_slice(size, keep, seed):
+    """A fixed sample of `keep` of `size` flat indices: every stride-th
+    element from a seeded offset.  A slice, so taking it costs neither
+    an index array nor a pass over the elements left out."""
+    import numpy as np
+
+    stride = max(1, size // keep)
+    first = int(np.random.default_rng(seed).integers(stride))
+    return slice(first, first + stride * keep, stride)
+
+
+def dump_outputs(out_dir, model, rank=0, world=1,
+                 budget_elems=_DUMP_BUDGET_ELEMS):
+    """Write the state the timed path hands back — per parameter, the
+    f32 master after the last step and the f32 gradient of that step —
+    as float32 .npy files.  Arrays are written whole while they fit the
+    64 MB budget; beyond it each array contributes a fixed, seeded
+    sample of its elements proportional to its size."""
+    import numpy as np
+
+    arrays = []
+    for i, p in enumerate(model.parameters()):
+        arrays.append((f"param_{i:02d}", p.data))
+        if p.grad is not None:
+            arrays.append((f"grad_{i:02d}", p.grad))
+    total = sum(t.numel() for _, t in arrays)
+    os.makedirs(out_dir, exist_ok=True)
+    prefix = f"rank{rank}_" if world > 1 else ""
+    for k, (name, t) in enumerate(arrays):
+        t = t.detach()
+        if total > budget_elems:
+            keep = max(1, t.numel() * budget_elems // total)
+            t = t.reshape(-1)[sample_slice(t.numel(), keep, 1000 + k)]
+        a = t.to(torch.float32).cpu().contiguous().numpy()
+        np.save(os.path.join(out_dir, prefix + name + ".npy"), a)
 
 
 def main():
@@ -51,7 +104,19 @@ def main():
                     help="bitwise-reproducible mode (split_k=1 wgrad)")
     ap.add_argument("--fp8-fwd", action="store_true",
                     help="MX-fp8 training forward on qualifying layers")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the last step's "
+                         "parameters and gradients as DIR/<name>.npy "
+                         "(float32, at most 64 MB in all); that step "
+                         "starts from the seeded initial weights so its "
+                         "inputs are the same in every run")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement beyond the headline "
+                         "figure (none exist today; a plain run is "
+                         "already the whole benchmark)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     from shallowspeed_amd.data import Dataset
     from shallowspeed_amd.models import MLP, SGD
@@ -136,14 +201,42 @@ def main():
         if is_gpu:
             torch.cuda.synchronize(device)
 
+    # --dump-outputs: the dumped step must be a function of the
+    # arguments.  Data and initial weights are seeded, but the default
+    # wgrad kernels combine split-K partial sums with f32 atomics, so
+    # every step's gradients carry arrival-order noise in their low
+    # bits, and bf16 training amplifies it step after step until two
+    # runs no longer agree to rounding.  So a dump run puts the seeded
+    # initial weights back just before its LAST timed step (clock
+    # stopped meanwhile): that step runs the very path the arguments
+    # select, on inputs that are identical from run to run, and what it
+    # leaves differs between runs only by one step's f32 summation order.
+    init_weights = None
+    if args.dump_outputs:
+        init_weights = [p.data.clone() for p in model.parameters()]
+
+    def restore_init_weights():
+        for p, w0 in zip(model.parameters(), init_weights):
+            p.data.copy_(w0)
+            p.sync_lp()
+        if hasattr(model, "invalidate_fp8"):
+            model.invalidate_fp8()
+
     for i in range(args.warmup):
         one_step(i)
     barrier_sync()
+    paused = 0.0
     t0 = time.perf_counter()
     for i in range(args.steps):
+        if init_weights is not None and i == args.steps - 1:
+            barrier_sync()
+            t_pause = time.perf_counter()
+            restore_init_weights()
+            barrier_sync()
+            paused = time.perf_counter() - t_pause
         one_step(i)
     barrier_sync()
-    elapsed = time.perf_counter() - t0
+    elapsed = time.perf_counter() - t0 - paused
 
     # MAX elapsed over ranks
     if topo.is_distributed:
@@ -155,6 +248,9 @@ def main():
     samples = global_batch * args.steps
     value = samples / elapsed
     ms_per_step = elapsed / args.steps * 1e3
+
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, model, topo.rank, topo.world)
 
     if topo.rank == 0:
         print(json.dumps({
@@ -187,6 +283,7 @@ def main():
                 "mubatches": args.mubatches,
                 "hipgraph": use_graph,
                 "fp8_fwd": args.fp8_fwd,
+                "deterministic": args.deterministic,
                 "peak_mem_gb": (round(torch.cuda.max_memory_allocated()
                                       / 2**30, 2) if is_gpu else None),
             },

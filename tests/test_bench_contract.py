@@ -5,6 +5,7 @@ import json
 import subprocess
 import sys
 
+import pytest
 import torch
 
 from shallowspeed_amd.models import MLP
@@ -35,6 +36,158 @@ def test_bench_json_contract():
     for key in ("model", "global_batch", "parallelism"):
         assert key in j["config"], key
     assert j["config"]["global_batch"] == 256
+
+
+def test_bench_dump_outputs_reproducible(tmp_path):
+    """--dump-outputs writes the last step's parameters and gradients as
+    float32 .npy; same arguments -> same inputs -> same outputs (the CPU
+    path is deterministic, so equality is exact).  --full is accepted
+    and leaves the result line's contract intact."""
+    import numpy as np
+
+    dumps = []
+    for tag, extra in (("a", []), ("b", ["--full"])):
+        d = tmp_path / tag
+        out = subprocess.run(
+            [sys.executable, "bench.py", "--gpus", "1", "--steps", "2",
+             "--warmup", "1", "--local-batch", "64", "--layer-sizes",
+             "24,16,10", "--device", "cpu", "--dump-outputs", str(d)]
+            + extra,
+            capture_output=True, text=True, timeout=300, check=True,
+        ).stdout.splitlines()
+        payload = [l for l in out if l.startswith("{")]
+        assert len(payload) == 1, out
+        j = json.loads(payload[0])
+        assert j["steps"] == 2 and j["ms_per_step"] > 0
+        assert j["config"]["parallelism"] == "dp1"
+        dumps.append({p.name: np.load(p) for p in sorted(d.iterdir())})
+    a, b = dumps
+    # 2 Linear layers x (weight, bias) x (param, grad)
+    assert sorted(a) == sorted(b) and len(a) == 8, sorted(a)
+    shapes = sorted(v.shape for v in a.values())
+    assert shapes == sorted(2 * [(16, 24), (16,), (10, 16), (10,)]), shapes
+    for name in a:
+        assert a[name].dtype == np.float32, name
+        assert np.isfinite(a[name]).all(), name
+        np.testing.assert_array_equal(a[name], b[name], err_msg=name)
+    # the steps really ran: gradients are not all zero
+    assert any(np.abs(v).max() > 0 for k, v in a.items()
+               if k.startswith("grad_"))
+
+
+def test_bench_rejects_zero_steps():
+    r = subprocess.run(
+        [sys.executable, "bench.py", "--steps", "0", "--device", "cpu"],
+        capture_output=True, text=True, timeout=300)
+    assert r.returncode == 2, r
+    assert "--steps must be at least 1" in r.stderr
+    assert "Traceback" not in r.stderr and "{" not in r.stdout
+
+
+def test_dump_outputs_sampling_branch(tmp_path):
+    """Over the size budget every array is cut to a fixed, seeded sample
+    proportional to its size: within budget in all, the same elements
+    on every call, and elements of the source at the sampled places."""
+    import numpy as np
+
+    import bench
+
+    m = MLP([24, 16, 10], 0, 1, 8)
+    g = torch.Generator().manual_seed(5)
+    for p in m.parameters():
+        p.grad.copy_(torch.randn(p.grad.shape, generator=g))
+    total = 2 * sum(p.data.numel() for p in m.parameters())
+    budget = total // 4
+    for tag in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / tag), m, budget_elems=budget)
+    a = {f.name: np.load(f) for f in sorted((tmp_path / "a").iterdir())}
+    b = {f.name: np.load(f) for f in sorted((tmp_path / "b").iterdir())}
+    assert sorted(a) == sorted(b) and len(a) == 8
+    assert 0 < sum(v.size for v in a.values()) <= budget
+    for i, p in enumerate(m.parameters()):
+        for kind, src in (("param", p.data), ("grad", p.grad)):
+            got = a[f"{kind}_{i:02d}.npy"]
+            np.testing.assert_array_equal(got, b[f"{kind}_{i:02d}.npy"])
+            flat = src.reshape(-1).numpy()
+            want = max(1, flat.size * budget // total)
+            assert got.dtype == np.float32 and got.shape == (want,)
+            sl = bench.sample_slice(flat.size, want, 1000 + 2 * i
+                                    + (kind == "grad"))
+            np.testing.assert_array_equal(got, flat[sl])
+            if want > 1:  # spread over the array, not a leading block
+                assert sl.step == flat.size // want
+    # under the budget the arrays are written whole
+    bench.dump_outputs(str(tmp_path / "c"), m)
+    c = np.load(tmp_path / "c" / "param_00.npy")
+    assert c.shape == (16, 24)
+
+
+_FLAGSHIP = [784, 256, 256, 256, 10]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("deterministic", [False, True],
+                         ids=["default", "deterministic"])
+def test_bench_dump_outputs_gpu(tmp_path, gpu_device, deterministic):
+    """--dump-outputs at the flagship shape dumps the path the arguments
+    select — the split-K atomic wgrad path unless --deterministic is
+    passed — and two runs with the same arguments agree.
+
+    The dumped step starts from the seeded initial weights, and forward,
+    dgrad, loss head and SGD have fixed tile ownership, so two default
+    runs differ only by the order in which one step's S split-K partial
+    sums reach each f32 gradient element: |dg| <= 2*S*2^-24*A, with A
+    the sum of the partials' magnitudes.  S is at most one partial per
+    CU (256 = 2^8), which gives 2^-15*A; allowing cancellation to make A
+    up to 8x the array's largest element, the bound used is
+    2^-12*max|g| per array (1/16 of a bf16 ulp of that element — a
+    flipped bf16 rounding or a lower-precision kernel is far above it).
+    The weights then differ by lr*dg (lr = 1e-3) plus the f32 rounding
+    of the update, 2^-22*max|w| (biases start at zero, so max|w| is
+    taken over the weights before and after the step).  The same
+    rounding bound ties the dump to its definition: w == w0 - lr*g.
+    Under --deterministic the files are byte-identical."""
+    import numpy as np
+
+    dumps = []
+    for tag in ("a", "b"):
+        d = tmp_path / tag
+        out = subprocess.run(
+            [sys.executable, "bench.py", "--gpus", "1", "--steps", "6",
+             "--warmup", "2", "--dump-outputs", str(d)]
+            + (["--deterministic"] if deterministic else []),
+            capture_output=True, text=True, timeout=300, check=True,
+        ).stdout.splitlines()
+        j = json.loads([l for l in out if l.startswith("{")][0])
+        assert j["dtype"] == "bf16" and j["steps"] == 6
+        assert j["config"]["deterministic"] is deterministic
+        dumps.append({p.name: np.load(p) for p in sorted(d.iterdir())})
+    a, b = dumps
+    assert sorted(a) == sorted(b) and len(a) == 16, sorted(a)
+    w0 = [p.data.numpy() for p in MLP(_FLAGSHIP, 0, 1, 16384).parameters()]
+    for i in range(8):
+        ga, gb = a[f"grad_{i:02d}.npy"], b[f"grad_{i:02d}.npy"]
+        wa, wb = a[f"param_{i:02d}.npy"], b[f"param_{i:02d}.npy"]
+        for x in (ga, wa):
+            assert x.dtype == np.float32 and x.shape == w0[i].shape
+            assert np.isfinite(x).all()
+        assert np.abs(ga).max() > 0, i
+        gtol = 2.0 ** -12 * np.abs(ga).max()
+        wtol = 2.0 ** -22 * max(np.abs(w0[i]).max(), np.abs(wa).max())
+        dg = np.abs(ga.astype(np.float64) - gb).max()
+        dw = np.abs(wa.astype(np.float64) - wb).max()
+        # the dumped step is one SGD step from the seeded weights
+        ds = np.abs(w0[i].astype(np.float64) - 1e-3 * ga - wa).max()
+        print(f"array {i}: max|g|={np.abs(ga).max():.3e} dg={dg:.3e} "
+              f"(tol {gtol:.3e}) dw={dw:.3e} step-residual={ds:.3e} "
+              f"(tol {wtol:.3e})")
+        if deterministic:
+            assert ga.tobytes() == gb.tobytes(), i
+            assert wa.tobytes() == wb.tobytes(), i
+        else:
+            assert dg <= gtol, (i, dg, gtol)
+            assert dw <= 1e-3 * gtol + wtol, (i, dw, gtol, wtol)
+        assert ds <= wtol, (i, ds, wtol)
 
 
 def test_model_hash_detects_changes():
