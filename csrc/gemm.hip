@@ -6,11 +6,8 @@
 //               with an optional fused ReLU-backward mask applied to A
 //               while staging (mask = stashed post-ReLU output, same
 //               shape as A).
-//   * wgrad_tn: gW[Mo,N] += (A[Kb,Mo] ⊙ mask)^T · B[Kb,N], split-K over
-//               the batch with f32 atomicAdd — the atomic IS the
-//               gradient accumulation across µbatches/split-K slices
-//               (reference grad accumulation: layers.py:135-136).
 //   * colsum:   gb[N] += Σ_rows (dY ⊙ mask) — bias grad.
+// (wgrad_tn, the weight-gradient TN GEMM, lives in wgrad.hip.)
 //
 // Design notes (cdna_hip_programming.md):
 //   * mfma_f32_16x16x32_bf16: per-wave 16×16 tile, K=32 per issue;
@@ -234,12 +231,10 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64) void gemm_nt_kernel(
     }
 }
 
-// 256-tile 8-phase tiers (gemm256.hip / wgrad256.hip) — C++ linkage,
-// declared OUTSIDE the extern "C" launcher block below
+// 256-tile 8-phase tier (gemm256.hip) — C++ linkage, declared OUTSIDE
+// the extern "C" launcher block below
 bool ss_gemm_nt_256(const void*, const void*, const void*, void*, int, int,
                     int, bool, hipStream_t);
-bool ss_wgrad_tn_256(const void*, const void*, void*, int, int, int,
-                     hipStream_t);
 
 // ------------------------------------------------- gemm_nt (glds tier)
 
@@ -364,282 +359,6 @@ __global__ __launch_bounds__(256) void gemm_nt_glds_kernel(
                 if constexpr (RELU) v = v > 0.f ? v : 0.f;
                 C[(long)grow * N + gcol] = f2bf(v);
             }
-        }
-    }
-}
-
-// ---------------------------------------------------------------- wgrad
-
-template <int BMT, int BNT, bool HAS_MASK>
-__global__ __launch_bounds__(256) void wgrad_tn_kernel(
-    const __bf16* __restrict__ dY,    // [Kb][Mo]
-    const __bf16* __restrict__ X,     // [Kb][N]
-    const __bf16* __restrict__ mask,  // [Kb][Mo]
-    float* __restrict__ gW,           // [Mo][N] (atomicAdd +=)
-    float* __restrict__ gb,           // [Mo] or null: fused bias grad
-    int Mo, int N, int Kb, int k_per_split,
-    // optional CHUNK TABLE (deferred µbatch wgrad): int64 rows of
-    // {dY*, X*, mask*}; grid.z covers chunks*split and each chunk is
-    // an independent [Kb][*] pair accumulated into the same gW/gb —
-    // ONE launch replaces num_µbatches launches per layer.
-    const long* __restrict__ chunks, int nsplit) {
-    // TN GEMM over the batch axis.  Tiles are staged in a BLOCKED
-    // [BKW/4][rows/16][4][16] bf16 layout so that
-    //   * staging is plain 16-B vector writes (global rows are
-    //     m/n-contiguous — no software transpose), and
-    //   * MFMA A/B fragments come out of LDS through the gfx950
-    //     HARDWARE transpose read ds_read_b64_tr_b16
-    //     (__builtin_amdgcn_ds_read_tr16_b64_v4bf16): each 16-lane
-    //     group hands the crossbar one [4][16] subtile and receives
-    //     its column — semantics verified on hardware by
-    //     scripts/probe_tr.hip.
-    // The 128x128 instantiation halves both operands' L2 re-reads for
-    // wide layers (traffic ∝ dY·(N/BNT) + X·(Mo/BMT)).
-    constexpr int BKW = 64;        // K-step (batch rows per stage)
-    constexpr int NMA = BMT / 16;  // 16-row blocks per A tile
-    constexpr int NMB = BNT / 16;
-    constexpr int FM = BMT / 32;   // 16x16 frags per wave (2x2 waves)
-    constexpr int FN = BNT / 32;
-
-    __shared__ ushort At[NMA * 16 * 64];  // dY^T tile, blocked+bit-swapped
-    __shared__ ushort Bt[NMB * 16 * 64];  // X^T tile, blocked+bit-swapped
-    __shared__ float dbs[256 / BMT > 1 ? 256 / BMT : 2][BMT];
-
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = tid >> 6;
-    const int wm = wave >> 1;  // 2x2 waves
-    const int wn = wave & 1;
-    // XCD-aware block remap (T1, bijective variant): the dispatcher
-    // places hw block b on XCD b%8; remap so each XCD owns a
-    // CONTIGUOUS run of work ids decoded n-tile-fastest — blocks that
-    // share a dY m-slice then read it from ONE XCD's L2 instead of
-    // filling all eight.
-    const int gx = gridDim.x, gy = gridDim.y;
-    const int nwg = gx * gy * gridDim.z;
-    const int hw = blockIdx.x + gx * (blockIdx.y + gy * blockIdx.z);
-    const int xcd = hw % 8, q = nwg / 8, r = nwg % 8;
-    const int wid = (xcd < r ? xcd * (q + 1)
-                             : r * (q + 1) + (xcd - r) * q) + hw / 8;
-    const int bidy = wid % gy;
-    const int bidx = (wid / gy) % gx;
-    int bidz = wid / (gy * gx);
-    if (chunks) {
-        const long* row = chunks + (long)(bidz / nsplit) * 3;
-        dY = (const __bf16*)row[0];
-        X = (const __bf16*)row[1];
-        mask = (const __bf16*)row[2];
-        bidz = bidz % nsplit;
-    }
-    const int m0 = bidx * BMT;
-    const int n0 = bidy * BNT;
-    const int kbeg = bidz * k_per_split;
-    const int kend = min(Kb, kbeg + k_per_split);
-
-    f32x4 acc[FM][FN];
-#pragma unroll
-    for (int i = 0; i < FM; ++i)
-#pragma unroll
-        for (int j = 0; j < FN; ++j) acc[i][j] = {0.f, 0.f, 0.f, 0.f};
-
-    const bool do_db = (gb != nullptr) && (bidy == 0);
-    float db_part = 0.f;
-
-    // mblk-major image with the ksub bits 0,1 SWAPPED in the subtile
-    // position (wgrad256.hip's placement): the four tr-read lane
-    // groups (k-stride 2) then land on {row even|odd} x {phase 0|1}
-    // of the 256-B bank rows — the optimal 2-clk pattern with NO
-    // padding (the old 144-B-padded image left a 4-deep overlap on
-    // banks 24-31).
-    auto swsub = [](int ksub) {
-        return (ksub & ~3) | ((ksub & 1) << 1) | ((ksub >> 1) & 1);
-    };
-    auto baddrA = [swsub](int k, int m) {
-        return ((m >> 4) * 16 + swsub(k >> 2)) * 64 + (k & 3) * 16 + (m & 15);
-    };
-    auto baddrB = [swsub](int k, int m) {
-        return ((m >> 4) * 16 + swsub(k >> 2)) * 64 + (k & 3) * 16 + (m & 15);
-    };
-
-    // staging: thread t covers ELA contiguous elems of the [BKW][BMT]
-    // tile (vector fast path when fully in range)
-    constexpr int ELA = BKW * BMT / 256;
-    constexpr int ELB = BKW * BNT / 256;
-    const int ska = (tid * ELA) / BMT, sma = (tid * ELA) % BMT;
-    const int skb = (tid * ELB) / BNT, smb = (tid * ELB) % BNT;
-
-    // glds staging (unmasked full tiles): the padded blocked image is
-    // 9 aligned 16-B pieces per 144-B subtile (8 data + 1 pad), so a
-    // per-lane SOURCE scatter performs the transpose while the LDS
-    // dest stays lane-linear; lanes landing on the pad piece load a
-    // dummy in-bounds address.  piece p -> subtile s=p/9, r=p%9;
-    // r<8: k = (s/NMT)*4 + (r>>1), m = (s%NMT)*16 + (r&1)*8.
-    typedef __attribute__((address_space(1))) const unsigned int* ggptr_t;
-    typedef __attribute__((address_space(3))) unsigned int* glptr_t;
-    // unpadded image: subtile = exactly 8 aligned 16-B pieces, so the
-    // per-lane source scatter (the transpose) has NO pad lanes; piece
-    // q -> position p = q/8 (mblk = p/16, ksub = swsub(p&15)), r = q%8
-    // -> global (k = ksub*4 + (r>>1), m = mblk*16 + (r&1)*8).
-    auto glds_stage = [&](const __bf16* __restrict__ src, ushort* img,
-                          int nmt, int ld, int base_col, int gk0) {
-        const int total = nmt * 16 * 8;          // pieces
-        const int per_wave = total / 4;          // 4 waves
-        for (int i0 = 0; i0 < per_wave; i0 += 64) {
-            const int q = wave * per_wave + i0 + lane;
-            const int p = q >> 3, rr = q & 7;
-            const int ksub = ((p & 15) & ~3) | (((p & 15) & 1) << 1) |
-                             (((p & 15) >> 1) & 1);
-            const int k = ksub * 4 + (rr >> 1);
-            const int m = (p >> 4) * 16 + (rr & 1) * 8;
-            __builtin_amdgcn_global_load_lds(
-                (ggptr_t)(src + (gk0 + k) * ld + base_col + m),
-                (glptr_t)(img + (long)(wave * per_wave + i0) * 8), 16, 0,
-                0);
-        }
-    };
-
-    for (int k0 = kbeg; k0 < kend; k0 += BKW) {
-        const bool full_tile = !HAS_MASK && m0 + BMT <= Mo &&
-                               n0 + BNT <= N && k0 + BKW <= kend;
-        if (full_tile) {
-            glds_stage(dY, At, NMA, Mo, m0, k0);
-            glds_stage(X, Bt, NMB, N, n0, k0);
-            __syncthreads();  // drains the LDS-DMA (vmcnt inside)
-        } else {
-        {
-            const int gk = k0 + ska;
-            if (gk < kend && m0 + BMT <= Mo) {
-#pragma unroll
-                for (int ch = 0; ch < ELA; ch += 8) {
-                    bf16x8 v =
-                        *(const bf16x8*)&dY[(long)gk * Mo + m0 + sma + ch];
-                    if constexpr (HAS_MASK) {
-                        bf16x8 mk = *(const bf16x8*)&mask[(long)gk * Mo + m0 +
-                                                          sma + ch];
-#pragma unroll
-                        for (int i = 0; i < 8; ++i)
-                            if (!(bf2f(mk[i]) > 0.f)) v[i] = (__bf16)0.f;
-                    }
-                    *(bf16x8*)&At[baddrA(ska, sma + ch)] = v;
-                }
-            } else {
-#pragma unroll
-                for (int i = 0; i < ELA; ++i) {
-                    __bf16 v = (__bf16)0.f;
-                    const int gm = m0 + sma + i;
-                    if (gk < kend && gm < Mo) {
-                        v = dY[(long)gk * Mo + gm];
-                        if constexpr (HAS_MASK) {
-                            if (!(bf2f(mask[(long)gk * Mo + gm]) > 0.f))
-                                v = (__bf16)0.f;
-                        }
-                    }
-                    At[baddrA(ska, sma + i)] = *(const ushort*)&v;
-                }
-            }
-        }
-        {
-            const int gk = k0 + skb;
-            if (gk < kend && n0 + BNT <= N) {
-#pragma unroll
-                for (int ch = 0; ch < ELB; ch += 8) {
-                    bf16x8 v =
-                        *(const bf16x8*)&X[(long)gk * N + n0 + smb + ch];
-                    *(bf16x8*)&Bt[baddrB(skb, smb + ch)] = v;
-                }
-            } else {
-#pragma unroll
-                for (int i = 0; i < ELB; ++i) {
-                    __bf16 v = (__bf16)0.f;
-                    const int gn = n0 + smb + i;
-                    if (gk < kend && gn < N) v = X[(long)gk * N + gn];
-                    Bt[baddrB(skb, smb + i)] = *(const ushort*)&v;
-                }
-            }
-        }
-        __syncthreads();
-        }
-
-        if (do_db) {
-            constexpr int NKQ = 256 / BMT;       // threads stacked on k
-            constexpr int KPT = BKW / NKQ;       // k values per thread
-            const int m = tid % BMT, kq = tid / BMT;
-#pragma unroll
-            for (int j = 0; j < KPT; ++j) {
-                const ushort u = At[baddrA(kq * KPT + j, m)];
-                db_part += bf2f(*(const __bf16*)&u);
-            }
-        }
-
-        // ---- fragments via hardware transpose read ----
-        typedef __attribute__((address_space(3))) bf16x4v* lds_v4p;
-        const int lcol4 = (lane & 15) * 4;
-#pragma unroll
-        for (int kk = 0; kk < BKW / 32; ++kk) {
-            const int g2 = kk * 8 + (lane >> 4) * 2;  // k-subtile pair
-            bf16x8 a_frag[FM], b_frag[FN];
-#pragma unroll
-            for (int i = 0; i < FM; ++i) {
-                const int mblk = wm * FM + i;
-                bf16x4v lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(
-                    (lds_v4p)&At[(mblk * 16 + swsub(g2)) * 64 + lcol4]);
-                bf16x4v hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(
-                    (lds_v4p)&At[(mblk * 16 + swsub(g2 + 1)) * 64 + lcol4]);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    a_frag[i][e] = lo[e];
-                    a_frag[i][e + 4] = hi[e];
-                }
-            }
-#pragma unroll
-            for (int j = 0; j < FN; ++j) {
-                const int nblk = wn * FN + j;
-                bf16x4v lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(
-                    (lds_v4p)&Bt[(nblk * 16 + swsub(g2)) * 64 + lcol4]);
-                bf16x4v hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(
-                    (lds_v4p)&Bt[(nblk * 16 + swsub(g2 + 1)) * 64 + lcol4]);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    b_frag[j][e] = lo[e];
-                    b_frag[j][e + 4] = hi[e];
-                }
-            }
-#pragma unroll
-            for (int i = 0; i < FM; ++i)
-#pragma unroll
-                for (int j = 0; j < FN; ++j)
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-                        a_frag[i], b_frag[j], acc[i][j], 0, 0, 0);
-        }
-        __syncthreads();
-    }
-
-    const int lrow = lane & 15;
-    const int kch = lane >> 4;
-#pragma unroll
-    for (int i = 0; i < FM; ++i) {
-#pragma unroll
-        for (int j = 0; j < FN; ++j) {
-            const int gcol = n0 + wn * (BNT / 2) + j * 16 + lrow;
-            if (gcol >= N) continue;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int grow = m0 + wm * (BMT / 2) + i * 16 + kch * 4 + r;
-                if (grow >= Mo) continue;
-                atomicAdd(&gW[(long)grow * N + gcol], acc[i][j][r]);
-            }
-        }
-    }
-
-    if (do_db) {
-        constexpr int NKQ = 256 / BMT;
-        dbs[tid / BMT][tid % BMT] = db_part;
-        __syncthreads();
-        if (tid < BMT && m0 + tid < Mo) {
-            float s4 = 0.f;
-#pragma unroll
-            for (int q = 0; q < NKQ; ++q) s4 += dbs[q][tid];
-            atomicAdd(&gb[m0 + tid], s4);
         }
     }
 }
@@ -831,110 +550,6 @@ void ss_gemm_nt(const void* A, const void* B, const void* bias,
         DISPATCH(B64)
     }
 #undef DISPATCH
-}
-
-void ss_colsum(const void*, const void*, void*, int, int, hipStream_t);
-
-void ss_wgrad_tn(const void* dY, const void* X, const void* mask, void* gW,
-                 void* gb, int Mo, int N, int Kb, int split_k,
-                 hipStream_t stream) {
-    // widest tier first: 8-phase 256-tile TN kernel for aligned wide
-    // unmasked shapes (bias grad via the standalone colsum kernel).
-    // SS_WGRAD256=0 disables.
-    // >= 64 output tiles: below that the split-K short loops lose to
-    // the 128-tile kernel (measured 440 vs 514 TF at 1024^2 x 16384)
-    if (!mask && split_k <= 0 && Mo >= 512 && N >= 512 &&
-        (long)(Mo / 256) * (N / 256) >= 64) {
-        static int en = -1;
-        if (en < 0) {
-            const char* e = getenv("SS_WGRAD256");
-            en = e ? atoi(e) : 1;
-        }
-        if (en && ss_wgrad_tn_256(dY, X, gW, Mo, N, Kb, stream)) {
-            if (gb) ss_colsum(dY, nullptr, gb, Kb, Mo, stream);
-            return;
-        }
-    }
-    // big tiles only pay when both dims are wide enough that the
-    // grid still covers the CUs AND operand re-reads dominate
-    // (measured: at 256-wide layers the 64-config's block count wins)
-    bool big = (Mo >= 256 && N >= 512) || (Mo >= 512 && N >= 256);
-    // debug/tuning overrides (read once)
-    static int env_big = []() {
-        const char* e = getenv("SS_WGRAD_BIG");
-        return e ? atoi(e) : -1;
-    }();
-    if (env_big >= 0) big = env_big != 0;
-    // experimental 128x256 tile (halves dY re-reads when N spans many
-    // 128-tiles but Mo is narrow — the flagship first layer's
-    // 16384x256x784 masked wgrad): SS_WGRAD_N256=1 enables
-    static int env_n256 = []() {
-        const char* e = getenv("SS_WGRAD_N256");
-        return e ? atoi(e) : 0;
-    }();
-    const bool n256 = env_n256 && Mo >= 128 && N >= 640;
-    const int bm = n256 ? 128 : (big ? 128 : 64);
-    const int bn = n256 ? 256 : (big ? 128 : 64);
-    // pick split for ~512 blocks total (2 per CU): more split
-    // duplicates the atomic-epilogue traffic (measured: 1024² best at
-    // exactly the coverage split; over-splitting by K depth cost
-    // +50%), less starves the CUs
-    if (split_k <= 0) {
-        const int tiles = cdiv(Mo, bm) * cdiv(N, bn);
-        split_k = cdiv(512, tiles);
-        // round DOWN to a power of two (even k-slice boundaries;
-        // measured best at 256×784)
-        while (split_k & (split_k - 1)) split_k &= split_k - 1;
-        const int max_split = cdiv(Kb, 64);
-        if (split_k > max_split) split_k = max_split;
-    }
-    int k_per_split = cdiv(cdiv(Kb, split_k), 64) * 64;  // BKW=64
-    split_k = cdiv(Kb, k_per_split);
-    dim3 grid(cdiv(Mo, bm), cdiv(N, bn), split_k);
-    dim3 block(256);
-#define WLAUNCH(BMT, BNT, HM)                                               \
-    hipLaunchKernelGGL((wgrad_tn_kernel<BMT, BNT, HM>), grid, block, 0,     \
-                       stream, (const __bf16*)dY, (const __bf16*)X,         \
-                       (const __bf16*)mask, (float*)gW, (float*)gb, Mo, N,  \
-                       Kb, k_per_split, (const long*)nullptr, 1)
-    if (n256) {
-        if (mask) WLAUNCH(128, 256, true); else WLAUNCH(128, 256, false);
-    } else if (big) {
-        if (mask) WLAUNCH(128, 128, true); else WLAUNCH(128, 128, false);
-    } else {
-        if (mask) WLAUNCH(64, 64, true); else WLAUNCH(64, 64, false);
-    }
-#undef WLAUNCH
-}
-
-void ss_wgrad_tn_multi(const void* chunk_table, int nchunks, bool has_mask,
-                       void* gW, void* gb, int Mo, int N, int Kb_chunk,
-                       int split_k, hipStream_t stream) {
-    const bool big = (Mo >= 256 && N >= 512) || (Mo >= 512 && N >= 256);
-    const int bm = big ? 128 : 64, bn = big ? 128 : 64;
-    if (split_k <= 0) {
-        const int tiles = cdiv(Mo, bm) * cdiv(N, bn) * nchunks;
-        split_k = cdiv(512, tiles);
-        while (split_k & (split_k - 1)) split_k &= split_k - 1;
-        const int max_split = cdiv(Kb_chunk, 64);
-        if (split_k > max_split) split_k = max_split;
-    }
-    int k_per_split = cdiv(cdiv(Kb_chunk, split_k), 64) * 64;
-    split_k = cdiv(Kb_chunk, k_per_split);
-    dim3 grid(cdiv(Mo, bm), cdiv(N, bn), split_k * nchunks);
-    dim3 block(256);
-#define WLAUNCHM(BMT, BNT, HM)                                              \
-    hipLaunchKernelGGL((wgrad_tn_kernel<BMT, BNT, HM>), grid, block, 0,     \
-                       stream, (const __bf16*)nullptr,                      \
-                       (const __bf16*)nullptr, (const __bf16*)nullptr,      \
-                       (float*)gW, (float*)gb, Mo, N, Kb_chunk,             \
-                       k_per_split, (const long*)chunk_table, split_k)
-    if (big) {
-        if (has_mask) WLAUNCHM(128, 128, true); else WLAUNCHM(128, 128, false);
-    } else {
-        if (has_mask) WLAUNCHM(64, 64, true); else WLAUNCHM(64, 64, false);
-    }
-#undef WLAUNCHM
 }
 
 void ss_colsum(const void* dY, const void* mask, void* gb, int M, int N,

@@ -74,6 +74,7 @@ def build_ext(verbose=True):
     sources = [
         os.path.join(src_dir, "bindings.cpp"),
         os.path.join(src_dir, "gemm.hip"),
+        os.path.join(src_dir, "wgrad.hip"),
         os.path.join(src_dir, "gemm256.hip"),
         os.path.join(src_dir, "gemm256w.hip"),
         os.path.join(src_dir, "wgrad256.hip"),
