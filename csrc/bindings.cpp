@@ -59,6 +59,12 @@ bool ss_gemm_nt_f8(const void*, const void*, const void*, const void*,
 bool ss_gemm_nt_f8_q(const void*, const void*, const void*, const void*,
                      const void*, void*, void*, int, int, int, bool,
                      hipStream_t);
+// head.hip
+bool ss_head_fwd_fused(const void*, const void*, const void*, void*, int, int,
+                       int, int, hipStream_t);
+bool ss_head_bwd_fused(const void*, const void*, const void*, const void*,
+                       void*, void*, void*, void*, int, int, int, float, int,
+                       hipStream_t);
 
 namespace {
 
@@ -333,6 +339,81 @@ torch::Tensor head_xent_bwd(torch::Tensor s, torch::Tensor t,
     return dz;
 }
 
+void check_align16(const torch::Tensor& t, const char* name) {
+    TORCH_CHECK(((uintptr_t)t.data_ptr() & 15) == 0, name,
+                " must be 16-byte aligned");
+}
+
+// Fused classifier head (head.hip): probs = softmax(bf16(x @ w^T + b)).
+// rows_per_block: 0 = shipped choice, 32/64/128 = the measured arms.
+torch::Tensor head_fwd_fused(torch::Tensor x, torch::Tensor w,
+                             torch::Tensor b, int64_t rows_per_block) {
+    check_bf16(x, "x");
+    check_bf16(w, "w");
+    check_bf16(b, "b");
+    TORCH_CHECK(x.dim() == 2 && w.dim() == 2, "x/w must be 2-D");
+    const int M = x.size(0), K = x.size(1), C = w.size(0);
+    TORCH_CHECK(w.size(1) == K, "K mismatch: ", K, " vs ", w.size(1));
+    TORCH_CHECK(b.numel() == C, "bias size");
+    check_align16(x, "x");
+    check_align16(w, "w");
+    auto probs = torch::empty({M, C}, x.options());
+    TORCH_CHECK(ss_head_fwd_fused(x.data_ptr(), w.data_ptr(), b.data_ptr(),
+                                  probs.data_ptr(), M, K, C,
+                                  (int)rows_per_block, cur_stream()),
+                "shape outside the fused-head contract (C<=16, K%32==0, "
+                "K<=1024): ", M, "x", C, "x", K);
+    return probs;
+}
+
+// Fused head backward: dz = (probs - target)/GB, dx = dz @ W (w_t is the
+// transposed bf16 copy [K][C]); with non-empty grad tensors also
+// grad_w += dz^T @ x and grad_b += colsum(dz).  Returns (dz, dx).
+std::vector<torch::Tensor> head_bwd_fused(torch::Tensor probs,
+                                          torch::Tensor target,
+                                          torch::Tensor x, torch::Tensor w_t,
+                                          double global_batch,
+                                          torch::Tensor grad_w,
+                                          torch::Tensor grad_b,
+                                          int64_t rows_per_block) {
+    check_bf16(probs, "probs");
+    check_bf16(target, "target");
+    check_bf16(x, "x");
+    check_bf16(w_t, "w_t");
+    TORCH_CHECK(probs.dim() == 2 && x.dim() == 2 && w_t.dim() == 2,
+                "probs/x/w_t must be 2-D");
+    TORCH_CHECK(probs.sizes() == target.sizes(), "shape mismatch");
+    const int M = x.size(0), K = x.size(1), C = probs.size(1);
+    TORCH_CHECK(probs.size(0) == M, "batch mismatch");
+    TORCH_CHECK(w_t.size(0) == K && w_t.size(1) == C, "w_t must be [K][C]");
+    check_align16(x, "x");
+    void* gw_p = nullptr;
+    void* gb_p = nullptr;
+    if (has(grad_w)) {
+        check_f32(grad_w, "grad_w");
+        TORCH_CHECK(grad_w.dim() == 2 && grad_w.size(0) == C &&
+                        grad_w.size(1) == K, "grad_w shape");
+        gw_p = grad_w.data_ptr();
+        if (has(grad_b)) {
+            check_f32(grad_b, "grad_b");
+            TORCH_CHECK(grad_b.numel() == C, "grad_b size");
+            gb_p = grad_b.data_ptr();
+        }
+    } else {
+        TORCH_CHECK(!has(grad_b), "grad_b given without grad_w");
+    }
+    auto dz = torch::empty_like(probs);
+    auto dx = torch::empty({M, K}, x.options());
+    TORCH_CHECK(ss_head_bwd_fused(probs.data_ptr(), target.data_ptr(),
+                                  x.data_ptr(), w_t.data_ptr(), dz.data_ptr(),
+                                  dx.data_ptr(), gw_p, gb_p, M, K, C,
+                                  (float)(1.0 / global_batch),
+                                  (int)rows_per_block, cur_stream()),
+                "shape outside the fused-head contract (C<=16, K%32==0, "
+                "K<=1024): ", M, "x", C, "x", K);
+    return {dz, dx};
+}
+
 std::vector<torch::Tensor> ln_fwd(torch::Tensor x, torch::Tensor gamma,
                                   torch::Tensor beta, double eps) {
     check_bf16(x, "x");
@@ -514,6 +595,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("softmax_bwd", &softmax_bwd);
     m.def("head_mse_bwd", &head_mse_bwd);
     m.def("head_xent_bwd", &head_xent_bwd);
+    m.def("head_fwd_fused", &head_fwd_fused,
+          "fused head forward: softmax(bf16(x @ w^T + b))", py::arg("x"),
+          py::arg("w"), py::arg("b"), py::arg("rows_per_block") = 0);
+    m.def("head_bwd_fused", &head_bwd_fused,
+          "fused head backward -> (dz, dx); optional gW/gb accumulate",
+          py::arg("probs"), py::arg("target"), py::arg("x"), py::arg("w_t"),
+          py::arg("global_batch"), py::arg("grad_w"), py::arg("grad_b"),
+          py::arg("rows_per_block") = 0);
     m.def("sgd_multi", &sgd_multi);
     m.def("adamw_multi", &adamw_multi);
     m.def("transpose_bf16", &transpose_bf16);

@@ -1,0 +1,412 @@
+// Fused classifier head (gfx950 / MI355X): the last Linear (C <= 16
+// classes) together with the softmax-cross-entropy head, as ONE forward
+// and ONE backward kernel.
+//
+//   head_fwd_fused: probs = softmax(bf16(x · W^T + b))
+//   head_bwd_fused: dz = bf16((probs − target)/GB)
+//                   dx = bf16(dz · W)                 (B operand: W^T copy)
+//                   gW += dz^T · x ; gb += colsum(dz)  (optional, f32)
+//
+// Replaces gemm_nt → softmax_fwd and head_xent_bwd → gemm_nt(dz, Wt) →
+// wgrad_tn for this shape class.  Those kernels run far below any
+// hardware limit here (a 64-wide N tile for 10 columns, one wave per
+// softmax row with 10 live lanes, the logits and dz round-tripping
+// through memory between launches).
+//
+// probs, dz and dx are BIT-IDENTICAL to the unfused chain: the same
+// v_mfma_f32_16x16x32_bf16 with the same operand slots and K-step
+// order, the same bf16 rounding points (logits are rounded to bf16 and
+// widened again before the softmax), the same __expf / multiply, and
+// the same xor tree over the 16 lanes that hold one row (the unfused
+// tree's offsets 32 and 16 only add zeros for C <= 16).  gW / gb differ
+// from wgrad_tn only in f32 summation order.
+//
+// Launch contract (both kernels): C <= 16, K % 32 == 0, K <= 1024,
+// M >= 1.  The launchers return false outside it.
+
+#include "common.h"
+
+#include <cstdlib>
+
+namespace {
+
+__device__ __forceinline__ bf16x8 zero8() {
+    bf16x8 z;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) z[i] = (__bf16)0.f;
+    return z;
+}
+
+__device__ __forceinline__ ushort bf_bits(__bf16 v) {
+    return *(const ushort*)&v;
+}
+
+}  // namespace
+
+// ---------------------------------------------------------------- forward
+
+// One 16-column fragment per wave: wave w of a block owns FR fragments
+// of 16 rows.  The MFMA A operand of row r, K-step t is 16 contiguous
+// bytes of x per lane, so x goes global -> registers with 16-B loads
+// and no LDS; W (C x K, <= 32 KB, L2-resident) is read the same way as
+// the B operand, rows c >= C as zeros.  Up to 8 K-steps of loads are in
+// flight per wave before the first MFMA, and the next group is issued
+// ahead of the current group's MFMAs.  There is no barrier.
+template <int WAVES, int FR>
+__global__ __launch_bounds__(WAVES * 64) void head_fwd_fused_kernel(
+    const __bf16* __restrict__ x,     // [M][K]
+    const __bf16* __restrict__ W,     // [C][K]
+    const __bf16* __restrict__ bias,  // [C]
+    __bf16* __restrict__ probs,       // [M][C]
+    int M, int K, int C) {
+    constexpr int U = 8 / FR;  // K-steps per load group
+
+    const int lane = threadIdx.x & 63;
+    const int wave = threadIdx.x >> 6;
+    const int lrow = lane & 15;
+    const int kch = lane >> 4;
+    const int row_base = (blockIdx.x * WAVES + wave) * (16 * FR);
+    if (row_base >= M) return;  // wave-uniform
+
+    const bool cvalid = lrow < C;
+    const __bf16* xp[FR];
+#pragma unroll
+    for (int f = 0; f < FR; ++f)
+        xp[f] = x + (long)min(row_base + f * 16 + lrow, M - 1) * K + kch * 8;
+    const __bf16* wp = W + (long)min(lrow, C - 1) * K + kch * 8;
+
+    const int nsteps = K / 32;
+    bf16x8 a[FR][U], b[U], an[FR][U], bn[U];
+    auto load = [&](bf16x8(&aa)[FR][U], bf16x8(&bb)[U], int t0) {
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            if (t0 + u < nsteps) {
+#pragma unroll
+                for (int f = 0; f < FR; ++f)
+                    aa[f][u] = *(const bf16x8*)(xp[f] + (t0 + u) * 32);
+                bb[u] = *(const bf16x8*)(wp + (t0 + u) * 32);
+            }
+        }
+    };
+
+    f32x4 acc[FR];
+#pragma unroll
+    for (int f = 0; f < FR; ++f) acc[f] = {0.f, 0.f, 0.f, 0.f};
+
+    load(a, b, 0);
+    for (int t0 = 0; t0 < nsteps; t0 += U) {
+        const bool more = t0 + U < nsteps;
+        if (more) load(an, bn, t0 + U);
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            if (t0 + u < nsteps) {
+                const bf16x8 bv = cvalid ? b[u] : zero8();
+#pragma unroll
+                for (int f = 0; f < FR; ++f)
+                    acc[f] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+                        a[f][u], bv, acc[f], 0, 0, 0);
+            }
+        }
+        if (more) {
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+#pragma unroll
+                for (int f = 0; f < FR; ++f) a[f][u] = an[f][u];
+                b[u] = bn[u];
+            }
+        }
+    }
+
+    // ---- epilogue in registers: lane (kch, lrow) holds rows
+    // kch*4 + r of column lrow; the 16 lanes of one kch hold one row
+    const float bv = cvalid ? bf2f(bias[lrow]) : 0.f;
+#pragma unroll
+    for (int f = 0; f < FR; ++f) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            float v = acc[f][r];
+            v += bv;
+            v = bf2f(f2bf(v));  // the logit as the unfused path stores it
+            float m = cvalid ? fmaxf(-1e30f, v) : -1e30f;
+#pragma unroll
+            for (int off = 8; off > 0; off >>= 1)
+                m = fmaxf(m, __shfl_xor(m, off, 64));
+            const float e = cvalid ? __expf(v - m) : 0.f;
+            float s = e;
+#pragma unroll
+            for (int off = 8; off > 0; off >>= 1)
+                s += __shfl_xor(s, off, 64);
+            const float inv = 1.f / s;
+            const int row = row_base + f * 16 + kch * 4 + r;
+            if (cvalid && row < M)
+                probs[(long)row * C + lrow] = f2bf(e * inv);
+        }
+    }
+}
+
+// --------------------------------------------------------------- backward
+
+// A block walks row tiles of RB rows (with gW the grid is <= 256, so at
+// most 256 blocks add into any gradient element) and, for K > KC,
+// column chunks of KC.  Per tile:
+//   1. the x tile's global loads are issued (only when gW is wanted —
+//      wgrad is the only reason this kernel reads x),
+//   2. dz of the tile is computed, stored, and kept in LDS as bf16
+//      (MFMA A operand, class index = k slot, k >= C zero) and as f32,
+//   3. one MFMA per 16x16 dx fragment (B operand: W^T rows, staged once
+//      per chunk), the tile goes through LDS and out as 16-B
+//      row-contiguous stores,
+//   4. the x tile replaces the dx tile in LDS; thread k sums
+//      dz[r][c]·x[r][k] over the tile's rows into registers.
+// The register sums are added to gW once per block and chunk, row-
+// contiguously (a wave instruction covers 64 consecutive floats of one
+// gW row).
+template <int RB, int KC, int C4>
+__global__ __launch_bounds__(256) void head_bwd_fused_kernel(
+    const __bf16* __restrict__ probs,   // [M][C]
+    const __bf16* __restrict__ target,  // [M][C]
+    const __bf16* __restrict__ x,       // [M][K]
+    const __bf16* __restrict__ Wt,      // [K][C]
+    __bf16* __restrict__ dz,            // [M][C]
+    __bf16* __restrict__ dx,            // [M][K]
+    float* __restrict__ gW,             // [C][K] (atomicAdd +=) or null
+    float* __restrict__ gb,             // [C]    (atomicAdd +=) or null
+    int M, int K, int C, float inv_gb, int ntiles) {
+    constexpr int LDT = KC + 8;              // padded tile row (bf16)
+    constexpr int PPR = KC / 8;              // 16-B pieces per tile row
+    constexpr int NP = RB * PPR / 256;       // pieces per thread
+    constexpr int NRG = RB / 16;             // 16-row groups per tile
+    static_assert(RB * PPR % 256 == 0, "piece mapping");
+
+    __shared__ __attribute__((aligned(16))) ushort tile[RB][LDT];
+    __shared__ __attribute__((aligned(16))) ushort wts[KC][16];
+    __shared__ __attribute__((aligned(16))) ushort dzs[RB][16];
+    __shared__ __attribute__((aligned(16))) float dzf[RB][16];
+
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = tid >> 6;
+    const int lrow = lane & 15;
+    const int kch = lane >> 4;
+    const bool wg = gW != nullptr;  // block-uniform
+
+    float gbacc = 0.f;
+    for (int k0 = 0; k0 < K; k0 += KC) {
+        const int kc = min(KC, K - k0);  // multiple of 32
+        const bool first = k0 == 0;
+
+        // W^T rows of this chunk, zero-padded to 16 classes
+        if (tid < KC) {
+            __bf16 w[16];
+#pragma unroll
+            for (int c = 0; c < 16; ++c) {
+                w[c] = (__bf16)0.f;
+                if (tid < kc && c < C) w[c] = Wt[(long)(k0 + tid) * C + c];
+            }
+            bf16x8 lo, hi;
+#pragma unroll
+            for (int c = 0; c < 8; ++c) {
+                lo[c] = w[c];
+                hi[c] = w[c + 8];
+            }
+            *(bf16x8*)&wts[tid][0] = lo;
+            *(bf16x8*)&wts[tid][8] = hi;
+        }
+
+        float gw[C4 * 4];
+#pragma unroll
+        for (int c = 0; c < C4 * 4; ++c) gw[c] = 0.f;
+
+        for (int t = blockIdx.x; t < ntiles; t += gridDim.x) {
+            const int row0 = t * RB;
+
+            // 1. x tile -> registers (rows past M and columns past the
+            //    chunk as zeros)
+            bf16x8 xr[NP];
+            if (wg) {
+#pragma unroll
+                for (int i = 0; i < NP; ++i) {
+                    const int q = tid + i * 256;
+                    const int r = q / PPR, col = (q % PPR) * 8;
+                    xr[i] = zero8();
+                    if (row0 + r < M && col < kc)
+                        xr[i] = *(const bf16x8*)&x[(long)(row0 + r) * K + k0 +
+                                                    col];
+                }
+            }
+
+            // 2. dz of the tile
+            for (int e = tid; e < RB * 16; e += 256) {
+                const int r = e >> 4, c = e & 15;
+                float d = 0.f;
+                ushort bits = 0;
+                if (c < C && row0 + r < M) {
+                    const long gi = (long)(row0 + r) * C + c;
+                    const __bf16 o = f2bf(
+                        (bf2f(probs[gi]) - bf2f(target[gi])) * inv_gb);
+                    if (first) dz[gi] = o;
+                    d = bf2f(o);
+                    bits = bf_bits(o);
+                }
+                dzs[r][c] = bits;
+                dzf[r][c] = d;
+            }
+            __syncthreads();
+
+            // 3. dx fragments: acc starts at zero, ONE MFMA, k slot =
+            //    class index (lanes kch >= 2 hold k >= 16: zeros)
+            const int nfrag = NRG * (kc / 16);
+            for (int idx = wave; idx < nfrag; idx += 4) {
+                const int rg = idx % NRG, ct = idx / NRG;
+                bf16x8 af = zero8(), bfr = zero8();
+                if (kch < 2) {
+                    af = *(const bf16x8*)&dzs[rg * 16 + lrow][kch * 8];
+                    bfr = *(const bf16x8*)&wts[ct * 16 + lrow][kch * 8];
+                }
+                f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+                acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af, bfr, acc, 0,
+                                                              0, 0);
+#pragma unroll
+                for (int r = 0; r < 4; ++r)
+                    tile[rg * 16 + kch * 4 + r][ct * 16 + lrow] =
+                        bf_bits(f2bf(acc[r]));
+            }
+            __syncthreads();
+#pragma unroll
+            for (int i = 0; i < NP; ++i) {
+                const int q = tid + i * 256;
+                const int r = q / PPR, col = (q % PPR) * 8;
+                if (row0 + r < M && col < kc)
+                    *(bf16x8*)&dx[(long)(row0 + r) * K + k0 + col] =
+                        *(const bf16x8*)&tile[r][col];
+            }
+
+            // 4. weight and bias gradient of the tile
+            if (wg) {
+                __syncthreads();
+#pragma unroll
+                for (int i = 0; i < NP; ++i) {
+                    const int q = tid + i * 256;
+                    *(bf16x8*)&tile[q / PPR][(q % PPR) * 8] = xr[i];
+                }
+                __syncthreads();
+                if (tid < kc) {
+#pragma unroll 4
+                    for (int r = 0; r < RB; ++r) {
+                        const ushort u = tile[r][tid];
+                        const float xv = bf2f(*(const __bf16*)&u);
+#pragma unroll
+                        for (int g = 0; g < C4; ++g) {
+                            const float4 d = *(const float4*)&dzf[r][g * 4];
+                            gw[g * 4 + 0] += d.x * xv;
+                            gw[g * 4 + 1] += d.y * xv;
+                            gw[g * 4 + 2] += d.z * xv;
+                            gw[g * 4 + 3] += d.w * xv;
+                        }
+                    }
+                }
+                if (first && gb != nullptr && tid < 16) {
+                    float s = 0.f;
+                    for (int r = 0; r < RB; ++r) s += dzf[r][tid];
+                    gbacc += s;
+                }
+            }
+            __syncthreads();  // LDS is rewritten by the next tile
+        }
+
+        // ONE set of atomics per block and chunk
+        if (wg && tid < kc) {
+#pragma unroll
+            for (int c = 0; c < C4 * 4; ++c)
+                if (c < C) atomicAdd(&gW[(long)c * K + k0 + tid], gw[c]);
+        }
+        __syncthreads();  // wts is rewritten by the next chunk
+    }
+    if (wg && gb != nullptr && tid < C) atomicAdd(&gb[tid], gbacc);
+}
+
+// ---------------------------------------------------------------- launchers
+
+namespace {
+
+bool head_contract(int M, int K, int C) {
+    return M >= 1 && C >= 1 && C <= 16 && K >= 32 && K % 32 == 0 && K <= 1024;
+}
+
+// most blocks that may add into one gradient element: one per CU
+constexpr int HEAD_BWD_MAX_BLOCKS = 256;
+
+template <int RB, int KC>
+void head_bwd_launch(const void* probs, const void* target, const void* x,
+                     const void* Wt, void* dz, void* dx, void* gW, void* gb,
+                     int M, int K, int C, float inv_gb, hipStream_t st) {
+    const int ntiles = cdiv(M, RB);
+    // the cap only matters where blocks add into gW / gb
+    const dim3 grid(gW == nullptr || ntiles < HEAD_BWD_MAX_BLOCKS
+                        ? ntiles
+                        : HEAD_BWD_MAX_BLOCKS);
+#define HEAD_BWD_C4(C4V)                                                     \
+    hipLaunchKernelGGL((head_bwd_fused_kernel<RB, KC, C4V>), grid, dim3(256), \
+                       0, st, (const __bf16*)probs, (const __bf16*)target,   \
+                       (const __bf16*)x, (const __bf16*)Wt, (__bf16*)dz,     \
+                       (__bf16*)dx, (float*)gW, (float*)gb, M, K, C, inv_gb, \
+                       ntiles)
+    switch ((C + 3) / 4) {
+        case 1: HEAD_BWD_C4(1); break;
+        case 2: HEAD_BWD_C4(2); break;
+        case 3: HEAD_BWD_C4(3); break;
+        default: HEAD_BWD_C4(4); break;
+    }
+#undef HEAD_BWD_C4
+}
+
+}  // namespace
+
+// rows_per_block: 0 = the shipped choice; 32 / 64 / 128 select the
+// measured arms (scripts/microbench_head.py, docs/KERNELS.md)
+bool ss_head_fwd_fused(const void* x, const void* W, const void* bias,
+                       void* probs, int M, int K, int C, int rows_per_block,
+                       hipStream_t st) {
+    if (!head_contract(M, K, C)) return false;
+    const int rb = rows_per_block ? rows_per_block : 64;
+#define HEAD_FWD(WV, FRV)                                                    \
+    hipLaunchKernelGGL((head_fwd_fused_kernel<WV, FRV>),                     \
+                       dim3(cdiv(M, WV * FRV * 16)), dim3(WV * 64), 0, st,   \
+                       (const __bf16*)x, (const __bf16*)W,                   \
+                       (const __bf16*)bias, (__bf16*)probs, M, K, C)
+    if (rb == 32) HEAD_FWD(2, 1);
+    else if (rb == 64) HEAD_FWD(4, 1);
+    else if (rb == 128) HEAD_FWD(4, 2);
+    else return false;
+#undef HEAD_FWD
+    return true;
+}
+
+bool ss_head_bwd_fused(const void* probs, const void* target, const void* x,
+                       const void* Wt, void* dz, void* dx, void* gW, void* gb,
+                       int M, int K, int C, float inv_gb, int rows_per_block,
+                       hipStream_t st) {
+    if (!head_contract(M, K, C)) return false;
+    // without gW the grid is not capped: 32-row tiles put two blocks on
+    // a CU, whose load / MFMA / store phases then overlap
+    // SS_HEAD_BWD_ROWS (read once) overrides the choice for tuning.
+    static const int env_rows = [] {
+        const char* e = getenv("SS_HEAD_BWD_ROWS");
+        return e ? atoi(e) : 0;
+    }();
+    if (!rows_per_block) rows_per_block = env_rows;
+    const int rb = rows_per_block ? rows_per_block : (gW ? 64 : 32);
+    // the 128-row arm halves the column chunk to stay inside 64 KB of LDS
+    if (rb == 32)
+        head_bwd_launch<32, 256>(probs, target, x, Wt, dz, dx, gW, gb, M, K,
+                                 C, inv_gb, st);
+    else if (rb == 64)
+        head_bwd_launch<64, 256>(probs, target, x, Wt, dz, dx, gW, gb, M, K,
+                                 C, inv_gb, st);
+    else if (rb == 128)
+        head_bwd_launch<128, 128>(probs, target, x, Wt, dz, dx, gW, gb, M, K,
+                                  C, inv_gb, st);
+    else
+        return false;
+    return true;
+}

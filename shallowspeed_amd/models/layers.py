@@ -445,29 +445,99 @@ class Sequential(Module):
         # deferred path — round-1 deferred all grads to OptimizerStep).
         self._flush_in_backward = False
 
+    # Linear(activation=None) -> SoftmaxXent at the end of the chain may
+    # run as the fused head kernels (csrc/head.hip); subclasses whose
+    # last Linear is not a plain one opt out.
+    _fuse_head = True
+
+    def _head_pair(self):
+        """(last Linear, SoftmaxXent head) when the chain ends in that
+        pair, else None."""
+        if not self._fuse_head or len(self.layers) < 2:
+            return None
+        lin, head = self.layers[-2], self.layers[-1]
+        if type(head) is SoftmaxXent and type(lin) is Linear \
+                and lin.activation is None:
+            return lin, head
+        return None
+
     def forward(self, inputs, mubatch_id: int = 0):
         x = inputs
-        for layer in self.layers:
+        pair = self._head_pair()
+        n_plain = len(self.layers) - 2 if pair else len(self.layers)
+        for layer in self.layers[:n_plain]:
             x = layer.forward(x, mubatch_id)
+        if pair:
+            lin, head = pair
+            if F.head_fused_ok(x, lin):
+                # same stashes as the two layers' own forwards, so
+                # either backward path can follow
+                lin._stash("x", mubatch_id, x)
+                s = F.head_fwd_fused(x, lin.weight.compute(),
+                                     lin.bias.compute())
+                head._stash("s", mubatch_id, s)
+                return s
+            x = head.forward(lin.forward(x, mubatch_id), mubatch_id)
         return x
+
+    def _fire_grad_hooks(self, layer):
+        # deferred-wgrad final backward: complete this layer's grads
+        # NOW (before its grad hooks fire) so param_done sees final
+        # values and the bucket all-reduce launches mid-backward
+        if self._flush_in_backward and hasattr(layer, "flush_wgrad"):
+            layer.flush_wgrad()
+        for hook in self._grad_hooks:
+            for p in layer.parameters():
+                if p.requires_grad:
+                    hook(p)
+
+    def _backward_head_fused(self, lin, head, target, mubatch_id):
+        """Fused backward of the head pair; returns dx of the Linear.
+        The weight gradient can ride in the same kernel
+        (F.set_head_wgrad_fused) unless it is deferred (chunk kept for
+        the flush) or deterministic (the single-owner wgrad kernel
+        keeps the bitwise contract); otherwise the wgrad kernel takes
+        the fused kernel's dz."""
+        s = head._unstash("s", mubatch_id)
+        x = lin._unstash("x", mubatch_id)
+        if target.dtype != s.dtype:
+            target = target.to(s.dtype)
+        if not target.is_contiguous():
+            target = target.contiguous()
+        in_kernel = (F.head_wgrad_fused() and not lin._defer_wgrad
+                     and not F.deterministic())
+        dz, dx = F.head_bwd_fused(
+            s, target, x, lin.weight.compute_t(), head.global_batch_size,
+            lin.weight.grad if in_kernel else None,
+            lin.bias.grad if in_kernel else None)
+        if lin._defer_wgrad:
+            lin._wgrad_pending.append((dz, x, None))
+            if len(lin._wgrad_pending) >= lin._wgrad_window:
+                lin.flush_wgrad()
+        elif not in_kernel:
+            F.linear_wgrad_acc(dz, x, lin.weight.grad, lin.bias.grad)
+        self._fire_grad_hooks(head)
+        self._fire_grad_hooks(lin)
+        return dx
 
     def backward(self, dout, mubatch_id: int = 0):
         d = dout
-        for i in range(len(self.layers) - 1, -1, -1):
+        last = len(self.layers) - 1
+        pair = self._head_pair()
+        if pair:
+            lin, head = pair
+            x = lin._cache.get(("x", mubatch_id))
+            need_dx = not (last == 1 and self._skip_input_grad)
+            if x is not None and need_dx and F.head_fused_ok(x, lin):
+                d = self._backward_head_fused(lin, head, d, mubatch_id)
+                last -= 2
+        for i in range(last, -1, -1):
             layer = self.layers[i]
             if i == 0 and self._skip_input_grad and isinstance(layer, Linear):
                 d = layer.backward(d, mubatch_id, need_dx=False)
             else:
                 d = layer.backward(d, mubatch_id)
-            # deferred-wgrad final backward: complete this layer's grads
-            # NOW (before its grad hooks fire) so param_done sees final
-            # values and the bucket all-reduce launches mid-backward
-            if self._flush_in_backward and hasattr(layer, "flush_wgrad"):
-                layer.flush_wgrad()
-            for hook in self._grad_hooks:
-                for p in layer.parameters():
-                    if p.requires_grad:
-                        hook(p)
+            self._fire_grad_hooks(layer)
         for hook in self._post_grad_hooks:
             hook(self.parameters())
         return d

@@ -46,6 +46,51 @@ def deterministic() -> bool:
     return _DETERMINISTIC
 
 
+_HEAD_FUSED = None
+
+
+def set_head_fused(flag: bool):
+    """Run the classifier head (last Linear + softmax-cross-entropy) as
+    the two fused kernels of csrc/head.hip instead of the six-launch
+    chain.  probs, dz and dx are bit-identical either way; the head's
+    own gW/gb differ in f32 summation order only.  Default on;
+    SS_HEAD_FUSED=0 (read once) turns it off."""
+    global _HEAD_FUSED
+    _HEAD_FUSED = bool(flag)
+
+
+def head_fused() -> bool:
+    global _HEAD_FUSED
+    if _HEAD_FUSED is None:
+        import os
+
+        _HEAD_FUSED = os.environ.get("SS_HEAD_FUSED", "1") != "0"
+    return _HEAD_FUSED
+
+
+_HEAD_WGRAD_FUSED = None
+
+
+def set_head_wgrad_fused(flag: bool):
+    """Let the fused head backward also accumulate the head's gW/gb
+    (one f32 atomic set per block).  Default OFF: at the flagship shape
+    that is 256 partial sums per gradient element, and same-address f32
+    atomics complete one after another (~50 ns each, measured), so the
+    existing wgrad_tn launch (64 partials) is faster end to end — see
+    docs/KERNELS.md.  SS_HEAD_WGRAD_FUSED=1 (read once) turns it on."""
+    global _HEAD_WGRAD_FUSED
+    _HEAD_WGRAD_FUSED = bool(flag)
+
+
+def head_wgrad_fused() -> bool:
+    global _HEAD_WGRAD_FUSED
+    if _HEAD_WGRAD_FUSED is None:
+        import os
+
+        _HEAD_WGRAD_FUSED = os.environ.get("SS_HEAD_WGRAD_FUSED", "0") == "1"
+    return _HEAD_WGRAD_FUSED
+
+
 def _is_gpu(t: torch.Tensor) -> bool:
     return t.is_cuda
 
@@ -251,6 +296,42 @@ def head_softmax_xent_bwd(probs, target, global_batch):
     if _is_gpu(probs):
         return _ext_for(probs).head_xent_bwd(probs, target, float(global_batch))
     return (probs - target) / global_batch
+
+
+def head_fused_ok(x, linear) -> bool:
+    """True when `linear` (the Linear feeding a SoftmaxXent head) and
+    its input meet the launch contract of the fused head kernels:
+    GPU, bf16, no activation, no fp8 forward, out <= 16, in % 32 == 0,
+    in <= 1024."""
+    return (head_fused()
+            and _is_gpu(x) and x.dtype == torch.bfloat16 and x.dim() == 2
+            and x.shape[0] >= 1 and x.is_contiguous()
+            and x.data_ptr() % 16 == 0
+            and linear.activation is None and not linear.fp8_fwd
+            and linear.weight.lp is not None
+            and linear.weight.lp_t is not None
+            and linear.out_dims <= 16
+            and linear.in_dims % 32 == 0 and linear.in_dims <= 1024)
+
+
+def head_fwd_fused(x, w, b):
+    """probs = softmax(bf16(x @ W^T + b)) in one kernel (GPU only;
+    bit-identical to linear_fwd -> softmax_fwd)."""
+    return _ext_for(x).head_fwd_fused(x, w, b)
+
+
+def head_bwd_fused(probs, target, x, w_t, global_batch, grad_w=None,
+                   grad_b=None):
+    """(dz, dx) of the fused head in one kernel: dz = (probs - t)/GB,
+    dx = dz @ W — bit-identical to head_softmax_xent_bwd ->
+    linear_dgrad.  With grad_w (and grad_b) given, the same kernel also
+    accumulates grad_w += dz^T @ x and grad_b += colsum(dz) with f32
+    atomics (one set per block, at most 256 blocks)."""
+    empty = torch.Tensor()
+    return tuple(_ext_for(probs).head_bwd_fused(
+        probs, target, x, w_t, float(global_batch),
+        grad_w if grad_w is not None else empty,
+        grad_b if grad_b is not None else empty))
 
 
 def xent_loss(probs, target, global_batch, eps=1e-9):

@@ -171,6 +171,8 @@ class TPMLP(Sequential):
     """TP-sharded single-stage MLP with the standard loss head —
     drop-in for MLP when dp == pp == 1 and --tp > 1."""
 
+    _fuse_head = False  # the TP head keeps the unfused chain
+
     def __init__(self, sizes, tp_group, tp_rank, tp_world,
                  global_batch_size, loss="xent"):
         from ..models.layers import SoftmaxMSE, SoftmaxXent

@@ -125,6 +125,7 @@ class Worker:
             and self.topo.stage_id == self.topo.pp - 1
         )
         self._in_views = {}
+        self._gin_views = {}
         # deferred-µbatch wgrad: one chunked kernel per layer at the
         # optimizer step instead of a wgrad launch per µbatch
         self._defer_active = (
@@ -248,6 +249,7 @@ class Worker:
                 ops.append(("recv", self._in_bufs[cmd.buffer_idx],
                             self.topo.prev_rank))
             else:  # RecvOutputGrad
+                self._gin_views.pop(cmd.buffer_idx, None)
                 self._wait_buffer("gin", cmd.buffer_idx)
                 ops.append(("recv", self._gin_bufs[cmd.buffer_idx],
                             self.topo.next_rank))
@@ -262,8 +264,9 @@ class Worker:
 
     # -------------------------------------------------- hipGraph replay
     # The per-step kernel sequence is launch-bound at MLP scale
-    # (~20 small kernels/step); capturing it in a hipGraph collapses
-    # per-kernel host launch + boundary gaps into one replay
+    # (13 small kernels/step at the flagship); capturing it in a
+    # hipGraph collapses per-kernel host launch + boundary gaps into
+    # one replay
     # (MI355X price list: eager host launch ≈3.3-3.8 µs/kernel vs
     # graph replay ≈10-16 µs per whole step).
     #
@@ -419,9 +422,17 @@ class Worker:
             y = self._staged_y[cmd.mubatch_id * mb:(cmd.mubatch_id + 1) * mb]
         else:
             y = self.dataset.micro_batch_target(self._batch_id, cmd.mubatch_id)
-        self._wait_buffer("gin", cmd.buffer_idx)
         buf = self._gin_bufs[cmd.buffer_idx]
         assert y.shape == buf.shape, (y.shape, buf.shape)  # pipe.py:362-365
+        if y.dtype == self.compute_dtype and y.device == buf.device:
+            # zero-copy, as for the input: the loss head reads the
+            # dataset slice directly (the grad-in buffer exists for the
+            # RECV path; the last stage never receives).  The slice is
+            # read-only to the model.
+            self._gin_views[cmd.buffer_idx] = y
+            return
+        self._wait_buffer("gin", cmd.buffer_idx)
+        self._gin_views.pop(cmd.buffer_idx, None)
         with self._mu_ctx(cmd.mubatch_id):
             buf.copy_(y.to(self.compute_dtype), non_blocking=True)
 
@@ -435,6 +446,7 @@ class Worker:
                     self._out_bufs[cmd.buffer_idx], self.topo.next_rank)
 
     def _recv_output_grad(self, cmd):
+        self._gin_views.pop(cmd.buffer_idx, None)
         self._wait_buffer("gin", cmd.buffer_idx)
         comm_mod.recv_tensor(self._gin_bufs[cmd.buffer_idx], self.topo.next_rank)
 
@@ -465,7 +477,9 @@ class Worker:
     def _backward_acc(self, cmd, _mu_stream_ok=True):
         with (self._mu_ctx(cmd.mubatch_id) if _mu_stream_ok
               else contextlib.nullcontext()):
-            g = self._gin_bufs[cmd.out_buffer]
+            g = self._gin_views.get(cmd.out_buffer)
+            if g is None:
+                g = self._gin_bufs[cmd.out_buffer]
             if getattr(self, "_defer_active", False) and \
                     self.topo.stage_id != self.topo.pp - 1:
                 # non-last stages hand the RECV'D grad buffer to the
