@@ -9,6 +9,10 @@
 #include <ATen/cuda/CUDAContext.h>
 #include <hip/hip_runtime.h>
 
+#include <climits>
+#include <optional>
+#include <string>
+
 extern "C" {
 void ss_gemm_nt(const void*, const void*, const void*, const void*, void*,
                 int, int, int, bool, hipStream_t);
@@ -64,7 +68,9 @@ bool ss_head_fwd_fused(const void*, const void*, const void*, void*, int, int,
                        int, int, hipStream_t);
 bool ss_head_bwd_fused(const void*, const void*, const void*, const void*,
                        void*, void*, void*, void*, int, int, int, float, int,
-                       hipStream_t);
+                       void*, int, hipStream_t);
+bool ss_head_metrics(const void*, const void*, void*, int, int, int, int,
+                     hipStream_t);
 
 namespace {
 
@@ -339,6 +345,20 @@ torch::Tensor head_xent_bwd(torch::Tensor s, torch::Tensor t,
     return dz;
 }
 
+// Metrics accumulator (head.hip): int32 [slots][4], slots a power of
+// two; word 0 of a slot holds the bits of an f32.
+int check_metrics_acc(const torch::Tensor& acc) {
+    TORCH_CHECK(acc.is_cuda() && acc.scalar_type() == torch::kInt &&
+                    acc.is_contiguous() && acc.dim() == 2 &&
+                    acc.size(1) == 4,
+                "metrics accumulator must be CUDA int32 [slots][4]");
+    const int64_t slots = acc.size(0);
+    TORCH_CHECK(slots >= 1 && slots <= (1 << 20) &&
+                    (slots & (slots - 1)) == 0,
+                "metrics slots must be a power of two, got ", slots);
+    return (int)slots;
+}
+
 void check_align16(const torch::Tensor& t, const char* name) {
     TORCH_CHECK(((uintptr_t)t.data_ptr() & 15) == 0, name,
                 " must be 16-byte aligned");
@@ -375,7 +395,9 @@ std::vector<torch::Tensor> head_bwd_fused(torch::Tensor probs,
                                           double global_batch,
                                           torch::Tensor grad_w,
                                           torch::Tensor grad_b,
-                                          int64_t rows_per_block) {
+                                          int64_t rows_per_block,
+                                          std::optional<torch::Tensor> metrics,
+                                          int64_t slots) {
     check_bf16(probs, "probs");
     check_bf16(target, "target");
     check_bf16(x, "x");
@@ -402,16 +424,51 @@ std::vector<torch::Tensor> head_bwd_fused(torch::Tensor probs,
     } else {
         TORCH_CHECK(!has(grad_b), "grad_b given without grad_w");
     }
+    // metrics: the kernel also adds the batch's metric totals into this
+    // accumulator, using its first `slots` slots (0 = all of them)
+    void* met_p = nullptr;
+    int nslots = 1;
+    if (metrics.has_value()) {
+        nslots = check_metrics_acc(*metrics);
+        if (slots) {
+            TORCH_CHECK(slots >= 1 && slots <= nslots &&
+                            (slots & (slots - 1)) == 0,
+                        "slots must be a power of two <= ", nslots);
+            nslots = (int)slots;
+        }
+        met_p = metrics->data_ptr();
+    }
     auto dz = torch::empty_like(probs);
     auto dx = torch::empty({M, K}, x.options());
     TORCH_CHECK(ss_head_bwd_fused(probs.data_ptr(), target.data_ptr(),
                                   x.data_ptr(), w_t.data_ptr(), dz.data_ptr(),
                                   dx.data_ptr(), gw_p, gb_p, M, K, C,
                                   (float)(1.0 / global_batch),
-                                  (int)rows_per_block, cur_stream()),
+                                  (int)rows_per_block, met_p, nslots,
+                                  cur_stream()),
                 "shape outside the fused-head contract (C<=16, K%32==0, "
                 "K<=1024): ", M, "x", C, "x", K);
     return {dz, dx};
+}
+
+// Adds the metric totals of (probs, target) into acc: loss_sum (kind
+// "xent" or "mse"), argmax matches, rows, non-finite rows.
+void head_metrics(torch::Tensor probs, torch::Tensor target,
+                  torch::Tensor acc, const std::string& kind) {
+    check_bf16(probs, "probs");
+    check_bf16(target, "target");
+    TORCH_CHECK(probs.dim() == 2 && probs.sizes() == target.sizes(),
+                "probs/target must be 2-D of one shape");
+    TORCH_CHECK(kind == "xent" || kind == "mse", "kind must be xent or mse");
+    const int slots = check_metrics_acc(acc);
+    TORCH_CHECK(probs.size(0) >= 1 && probs.size(1) >= 1 &&
+                    probs.size(0) <= INT_MAX && probs.size(1) <= INT_MAX,
+                "empty or oversized probs");
+    TORCH_CHECK(ss_head_metrics(probs.data_ptr(), target.data_ptr(),
+                                acc.data_ptr(), slots, (int)probs.size(0),
+                                (int)probs.size(1), kind == "mse" ? 1 : 0,
+                                cur_stream()),
+                "head_metrics launch rejected");
 }
 
 std::vector<torch::Tensor> ln_fwd(torch::Tensor x, torch::Tensor gamma,
@@ -602,7 +659,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "fused head backward -> (dz, dx); optional gW/gb accumulate",
           py::arg("probs"), py::arg("target"), py::arg("x"), py::arg("w_t"),
           py::arg("global_batch"), py::arg("grad_w"), py::arg("grad_b"),
-          py::arg("rows_per_block") = 0);
+          py::arg("rows_per_block") = 0,
+          py::arg("metrics") = py::none(), py::arg("slots") = 0);
+    m.def("head_metrics", &head_metrics,
+          "metric totals of (probs, target) into a slotted accumulator",
+          py::arg("probs"), py::arg("target"), py::arg("acc"),
+          py::arg("kind") = "xent");
     m.def("sgd_multi", &sgd_multi);
     m.def("adamw_multi", &adamw_multi);
     m.def("transpose_bf16", &transpose_bf16);

@@ -23,9 +23,22 @@
 //
 // Launch contract (both kernels): C <= 16, K % 32 == 0, K <= 1024,
 // M >= 1.  The launchers return false outside it.
+//
+// Training metrics.  head_bwd_fused can also add the batch's loss sum,
+// argmax matches, row count and non-finite-row count into a slotted
+// accumulator (METRICS instantiations), and head_metrics_kernel does the
+// same for any (M, C) probs / target pair, cross-entropy or squared
+// error.  The accumulator is [S][4] 32-bit words, S a power of two:
+// word 0 f32 loss_sum, words 1..3 int32 correct, rows, nonfinite.  A
+// block adds its totals ONCE, into slot blockIdx.x % S, so that the
+// same-address atomics of a launch spread over S addresses; the host
+// folds the slots.  A row with a NaN or Inf prob counts in rows and
+// nonfinite only.
 
 #include "common.h"
 
+#include <climits>
+#include <cmath>
 #include <cstdlib>
 
 namespace {
@@ -39,6 +52,69 @@ __device__ __forceinline__ bf16x8 zero8() {
 
 __device__ __forceinline__ ushort bf_bits(__bf16 v) {
     return *(const ushort*)&v;
+}
+
+constexpr float SS_FLT_MIN = 1.17549435e-38f;
+
+__device__ __forceinline__ bool finite_f(float v) {
+    return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u;
+}
+
+// -t * log(max(p, FLT_MIN)); a zero target contributes nothing, so a
+// zero prob under it never makes 0 * log
+__device__ __forceinline__ float xent_term(float p, float t) {
+    return t == 0.f ? 0.f : -t * logf(fmaxf(p, SS_FLT_MIN));
+}
+
+// Sort key of a bf16 value in column c < 16: greater value first, then
+// lower column, so a max over keys is argmax with the lowest index
+// winning ties (-0 and +0 compare equal, as in a float compare).  Keys
+// of real columns are > 0; 0 stands for "no column".
+__device__ __forceinline__ unsigned argmax_key16(__bf16 v, int c) {
+    unsigned u = bf_bits(v);
+    if ((u & 0x7fffu) == 0) u = 0;
+    u = (u & 0x8000u) ? (~u & 0xffffu) : (u | 0x8000u);
+    return (u << 4) | (unsigned)(15 - c);
+}
+
+// The four totals of one block: the lanes that hold row results pass
+// theirs in, the wave sums go through `part` (16 words of LDS), and
+// after the caller's barrier head_metrics_commit adds them to the slot.
+__device__ __forceinline__ void head_metrics_wave_sums(float loss, int correct,
+                                                       int rows, int bad,
+                                                       int* part) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        loss += __shfl_xor(loss, off, 64);
+        correct += __shfl_xor(correct, off, 64);
+        rows += __shfl_xor(rows, off, 64);
+        bad += __shfl_xor(bad, off, 64);
+    }
+    if ((threadIdx.x & 63) == 0) {
+        int* w = part + (threadIdx.x >> 6) * 4;
+        w[0] = __float_as_int(loss);
+        w[1] = correct;
+        w[2] = rows;
+        w[3] = bad;
+    }
+}
+
+__device__ __forceinline__ void head_metrics_commit(const int* part,
+                                                    int* metrics, int slots) {
+    const int tid = threadIdx.x;
+    if (tid >= 4) return;
+    int* slot = metrics + (blockIdx.x & (slots - 1)) * 4;
+    if (tid == 0) {
+        float s = 0.f;
+#pragma unroll
+        for (int w = 0; w < 4; ++w) s += __int_as_float(part[w * 4]);
+        atomicAdd((float*)slot, s);
+    } else {
+        int s = 0;
+#pragma unroll
+        for (int w = 0; w < 4; ++w) s += part[w * 4 + tid];
+        atomicAdd(slot + tid, s);
+    }
 }
 
 }  // namespace
@@ -161,7 +237,16 @@ __global__ __launch_bounds__(WAVES * 64) void head_fwd_fused_kernel(
 // The register sums are added to gW once per block and chunk, row-
 // contiguously (a wave instruction covers 64 consecutive floats of one
 // gW row).
-template <int RB, int KC, int C4>
+//
+// METRICS: step 2 of the first chunk already holds probs[r][c] and
+// target[r][c] of a row in 16 adjacent lanes, so the row's loss term,
+// argmax match and finiteness are a 4-step xor reduction there.  The
+// lane of column 0 keeps the totals of its rows in registers over all
+// tiles of the block; after the first chunk's tile loop the wave sums
+// go to LDS, the barrier that ends every chunk carries them, and four
+// threads add them to the block's slot.  Later chunks recompute dz and
+// must not count again.
+template <int RB, int KC, int C4, bool METRICS>
 __global__ __launch_bounds__(256) void head_bwd_fused_kernel(
     const __bf16* __restrict__ probs,   // [M][C]
     const __bf16* __restrict__ target,  // [M][C]
@@ -171,6 +256,8 @@ __global__ __launch_bounds__(256) void head_bwd_fused_kernel(
     __bf16* __restrict__ dx,            // [M][K]
     float* __restrict__ gW,             // [C][K] (atomicAdd +=) or null
     float* __restrict__ gb,             // [C]    (atomicAdd +=) or null
+    int* __restrict__ metrics,          // [slots][4] (atomicAdd +=) or null
+    int slots,                          // power of two
     int M, int K, int C, float inv_gb, int ntiles) {
     constexpr int LDT = KC + 8;              // padded tile row (bf16)
     constexpr int PPR = KC / 8;              // 16-B pieces per tile row
@@ -182,6 +269,7 @@ __global__ __launch_bounds__(256) void head_bwd_fused_kernel(
     __shared__ __attribute__((aligned(16))) ushort wts[KC][16];
     __shared__ __attribute__((aligned(16))) ushort dzs[RB][16];
     __shared__ __attribute__((aligned(16))) float dzf[RB][16];
+    __shared__ int mpart[METRICS ? 16 : 1];
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -191,6 +279,8 @@ __global__ __launch_bounds__(256) void head_bwd_fused_kernel(
     const bool wg = gW != nullptr;  // block-uniform
 
     float gbacc = 0.f;
+    float m_loss = 0.f;
+    int m_correct = 0, m_rows = 0, m_bad = 0;
     for (int k0 = 0; k0 < K; k0 += KC) {
         const int kc = min(KC, K - k0);  // multiple of 32
         const bool first = k0 == 0;
@@ -240,16 +330,47 @@ __global__ __launch_bounds__(256) void head_bwd_fused_kernel(
                 const int r = e >> 4, c = e & 15;
                 float d = 0.f;
                 ushort bits = 0;
+                float term = 0.f;
+                unsigned pkey = 0, tkey = 0;
+                bool bad = false;
                 if (c < C && row0 + r < M) {
                     const long gi = (long)(row0 + r) * C + c;
-                    const __bf16 o = f2bf(
-                        (bf2f(probs[gi]) - bf2f(target[gi])) * inv_gb);
+                    const __bf16 pb = probs[gi], tb = target[gi];
+                    const __bf16 o = f2bf((bf2f(pb) - bf2f(tb)) * inv_gb);
                     if (first) dz[gi] = o;
                     d = bf2f(o);
                     bits = bf_bits(o);
+                    if (METRICS && first) {
+                        bad = !finite_f(bf2f(pb));
+                        term = xent_term(bf2f(pb), bf2f(tb));
+                        pkey = argmax_key16(pb, c);
+                        tkey = argmax_key16(tb, c);
+                    }
                 }
                 dzs[r][c] = bits;
                 dzf[r][c] = d;
+                if (METRICS && first) {  // block-uniform
+                    // the row's 16 lanes: e & 15 == lane & 15
+                    const bool rowbad =
+                        ((__ballot(bad) >> (lane & 48)) & 0xffffull) != 0;
+#pragma unroll
+                    for (int off = 8; off > 0; off >>= 1) {
+                        term += __shfl_xor(term, off, 64);
+                        pkey = max(pkey, (unsigned)__shfl_xor((int)pkey, off,
+                                                              64));
+                        tkey = max(tkey, (unsigned)__shfl_xor((int)tkey, off,
+                                                              64));
+                    }
+                    if (c == 0 && row0 + r < M) {
+                        m_rows += 1;
+                        if (rowbad) {
+                            m_bad += 1;
+                        } else {
+                            m_loss += term;
+                            m_correct += (pkey & 15u) == (tkey & 15u);
+                        }
+                    }
+                }
             }
             __syncthreads();
 
@@ -320,9 +441,86 @@ __global__ __launch_bounds__(256) void head_bwd_fused_kernel(
             for (int c = 0; c < C4 * 4; ++c)
                 if (c < C) atomicAdd(&gW[(long)c * K + k0 + tid], gw[c]);
         }
+        if (METRICS && first)
+            head_metrics_wave_sums(m_loss, m_correct, m_rows, m_bad, mpart);
         __syncthreads();  // wts is rewritten by the next chunk
+        if (METRICS && first) head_metrics_commit(mpart, metrics, slots);
     }
     if (wg && gb != nullptr && tid < C) atomicAdd(&gb[tid], gbacc);
+}
+
+// ---------------------------------------------------------------- metrics
+
+// The metric totals of any (M, C) probs / target pair: one wave per row,
+// four rows per block and pass, lanes strided over the columns like
+// row_argmax_kernel, rows walked grid-stride.  MSE selects the squared
+// error as the row loss, otherwise cross-entropy.  One atomic set per
+// block, into slot blockIdx.x % slots.
+template <bool MSE>
+__global__ __launch_bounds__(256) void head_metrics_kernel(
+    const __bf16* __restrict__ probs,   // [M][C]
+    const __bf16* __restrict__ target,  // [M][C]
+    int* __restrict__ metrics,          // [slots][4] (atomicAdd +=)
+    int slots, int M, int C) {
+    __shared__ int mpart[16];
+    const int lane = threadIdx.x & 63;
+    const int wave = threadIdx.x >> 6;
+
+    float m_loss = 0.f;
+    int m_correct = 0, m_rows = 0, m_bad = 0;
+    for (int row = blockIdx.x * 4 + wave; row < M; row += gridDim.x * 4) {
+        const __bf16* pr = probs + (long)row * C;
+        const __bf16* tr = target + (long)row * C;
+        float term = 0.f;
+        float pbest = -INFINITY, tbest = -INFINITY;
+        int pi = INT_MAX, ti = INT_MAX;
+        bool bad = false;
+        for (int c = lane; c < C; c += 64) {
+            const float p = bf2f(pr[c]), t = bf2f(tr[c]);
+            bad |= !finite_f(p);
+            if (MSE) term += (t - p) * (t - p);
+            else term += xent_term(p, t);
+            if (p > pbest || pi == INT_MAX) {
+                pbest = p;
+                pi = c;
+            }
+            if (t > tbest || ti == INT_MAX) {
+                tbest = t;
+                ti = c;
+            }
+        }
+        const bool rowbad = __ballot(bad) != 0;  // row is wave-uniform
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            term += __shfl_xor(term, off, 64);
+            const float pv = __shfl_xor(pbest, off, 64);
+            const int pj = __shfl_xor(pi, off, 64);
+            if (pj != INT_MAX &&
+                (pi == INT_MAX || pv > pbest || (pv == pbest && pj < pi))) {
+                pbest = pv;
+                pi = pj;
+            }
+            const float tv = __shfl_xor(tbest, off, 64);
+            const int tj = __shfl_xor(ti, off, 64);
+            if (tj != INT_MAX &&
+                (ti == INT_MAX || tv > tbest || (tv == tbest && tj < ti))) {
+                tbest = tv;
+                ti = tj;
+            }
+        }
+        if (lane == 0) {
+            m_rows += 1;
+            if (rowbad) {
+                m_bad += 1;
+            } else {
+                m_loss += term;
+                m_correct += pi == ti;
+            }
+        }
+    }
+    head_metrics_wave_sums(m_loss, m_correct, m_rows, m_bad, mpart);
+    __syncthreads();
+    head_metrics_commit(mpart, metrics, slots);
 }
 
 // ---------------------------------------------------------------- launchers
@@ -333,24 +531,33 @@ bool head_contract(int M, int K, int C) {
     return M >= 1 && C >= 1 && C <= 16 && K >= 32 && K % 32 == 0 && K <= 1024;
 }
 
+bool slots_ok(int slots) { return slots >= 1 && (slots & (slots - 1)) == 0; }
+
 // most blocks that may add into one gradient element: one per CU
 constexpr int HEAD_BWD_MAX_BLOCKS = 256;
 
 template <int RB, int KC>
 void head_bwd_launch(const void* probs, const void* target, const void* x,
                      const void* Wt, void* dz, void* dx, void* gW, void* gb,
-                     int M, int K, int C, float inv_gb, hipStream_t st) {
+                     void* metrics, int slots, int M, int K, int C,
+                     float inv_gb, hipStream_t st) {
     const int ntiles = cdiv(M, RB);
     // the cap only matters where blocks add into gW / gb
     const dim3 grid(gW == nullptr || ntiles < HEAD_BWD_MAX_BLOCKS
                         ? ntiles
                         : HEAD_BWD_MAX_BLOCKS);
+#define HEAD_BWD_K(C4V, MV)                                                  \
+    hipLaunchKernelGGL((head_bwd_fused_kernel<RB, KC, C4V, MV>), grid,       \
+                       dim3(256), 0, st, (const __bf16*)probs,               \
+                       (const __bf16*)target, (const __bf16*)x,              \
+                       (const __bf16*)Wt, (__bf16*)dz, (__bf16*)dx,          \
+                       (float*)gW, (float*)gb, (int*)metrics, slots, M, K,   \
+                       C, inv_gb, ntiles)
 #define HEAD_BWD_C4(C4V)                                                     \
-    hipLaunchKernelGGL((head_bwd_fused_kernel<RB, KC, C4V>), grid, dim3(256), \
-                       0, st, (const __bf16*)probs, (const __bf16*)target,   \
-                       (const __bf16*)x, (const __bf16*)Wt, (__bf16*)dz,     \
-                       (__bf16*)dx, (float*)gW, (float*)gb, M, K, C, inv_gb, \
-                       ntiles)
+    do {                                                                     \
+        if (metrics) HEAD_BWD_K(C4V, true);                                  \
+        else HEAD_BWD_K(C4V, false);                                         \
+    } while (0)
     switch ((C + 3) / 4) {
         case 1: HEAD_BWD_C4(1); break;
         case 2: HEAD_BWD_C4(2); break;
@@ -358,6 +565,7 @@ void head_bwd_launch(const void* probs, const void* target, const void* x,
         default: HEAD_BWD_C4(4); break;
     }
 #undef HEAD_BWD_C4
+#undef HEAD_BWD_K
 }
 
 }  // namespace
@@ -385,8 +593,9 @@ bool ss_head_fwd_fused(const void* x, const void* W, const void* bias,
 bool ss_head_bwd_fused(const void* probs, const void* target, const void* x,
                        const void* Wt, void* dz, void* dx, void* gW, void* gb,
                        int M, int K, int C, float inv_gb, int rows_per_block,
-                       hipStream_t st) {
+                       void* metrics, int slots, hipStream_t st) {
     if (!head_contract(M, K, C)) return false;
+    if (metrics && !slots_ok(slots)) return false;
     // without gW the grid is not capped: 32-row tiles put two blocks on
     // a CU, whose load / MFMA / store phases then overlap
     // SS_HEAD_BWD_ROWS (read once) overrides the choice for tuning.
@@ -398,15 +607,33 @@ bool ss_head_bwd_fused(const void* probs, const void* target, const void* x,
     const int rb = rows_per_block ? rows_per_block : (gW ? 64 : 32);
     // the 128-row arm halves the column chunk to stay inside 64 KB of LDS
     if (rb == 32)
-        head_bwd_launch<32, 256>(probs, target, x, Wt, dz, dx, gW, gb, M, K,
-                                 C, inv_gb, st);
+        head_bwd_launch<32, 256>(probs, target, x, Wt, dz, dx, gW, gb, metrics,
+                                 slots, M, K, C, inv_gb, st);
     else if (rb == 64)
-        head_bwd_launch<64, 256>(probs, target, x, Wt, dz, dx, gW, gb, M, K,
-                                 C, inv_gb, st);
+        head_bwd_launch<64, 256>(probs, target, x, Wt, dz, dx, gW, gb, metrics,
+                                 slots, M, K, C, inv_gb, st);
     else if (rb == 128)
-        head_bwd_launch<128, 128>(probs, target, x, Wt, dz, dx, gW, gb, M, K,
-                                  C, inv_gb, st);
+        head_bwd_launch<128, 128>(probs, target, x, Wt, dz, dx, gW, gb, metrics,
+                                  slots, M, K, C, inv_gb, st);
     else
         return false;
+    return true;
+}
+
+// kind: 0 = cross-entropy, 1 = squared error.  acc is [slots][4] words.
+bool ss_head_metrics(const void* probs, const void* target, void* acc,
+                     int slots, int M, int C, int kind, hipStream_t st) {
+    if (M < 1 || C < 1 || !slots_ok(slots) || (kind != 0 && kind != 1))
+        return false;
+    // enough blocks to fill the chip; more would only add atomics
+    const dim3 grid(min(cdiv(M, 4), 1024));
+    if (kind == 1)
+        hipLaunchKernelGGL(head_metrics_kernel<true>, grid, dim3(256), 0, st,
+                           (const __bf16*)probs, (const __bf16*)target,
+                           (int*)acc, slots, M, C);
+    else
+        hipLaunchKernelGGL(head_metrics_kernel<false>, grid, dim3(256), 0, st,
+                           (const __bf16*)probs, (const __bf16*)target,
+                           (int*)acc, slots, M, C);
     return true;
 }

@@ -82,3 +82,31 @@ def split_bwd():
 
 us = bench(split_bwd)
 print(f"bwd fused(no wgrad, 64) + wgrad_tn       : {us:6.1f} us")
+
+# training metrics: the accumulator's slot count S (a block adds into
+# slot blockIdx % S), in the fused backward and as the standalone launch
+acc = torch.zeros(256, 4, dtype=torch.int32, device=dev)
+for rb in (32, 64):
+    us = bench(lambda: e.head_bwd_fused(probs, t, x, w_t, float(M), empty,
+                                        empty, rb))
+    print(f"bwd fused, no wgrad, {rb:3d} rows, no metrics : {us:6.1f} us")
+    for S in (1, 16, 256):
+        us = bench(lambda: e.head_bwd_fused(probs, t, x, w_t, float(M),
+                                            empty, empty, rb, acc, S))
+        print(f"bwd fused, no wgrad, {rb:3d} rows, S = {S:3d}    : "
+              f"{us:6.1f} us")
+for S in (1, 16, 256):
+    a = acc[:S]
+    us = bench(lambda: e.head_metrics(probs, t, a, "xent"))
+    print(f"head_metrics standalone, xent, S = {S:3d}    : {us:6.1f} us")
+us = bench(lambda: e.head_metrics(probs, t, acc[:16], "mse"))
+print(f"head_metrics standalone, mse,  S =  16    : {us:6.1f} us")
+
+
+def bwd_then_metrics():
+    e.head_bwd_fused(probs, t, x, w_t, float(M), empty, empty, 32)
+    e.head_metrics(probs, t, acc[:16], "xent")
+
+
+us = bench(bwd_then_metrics)
+print(f"bwd fused(32, no metrics) + head_metrics : {us:6.1f} us")

@@ -381,7 +381,15 @@ class _LossHead(Module):
     dout argument (reference layers.py:157-163) and emits d(logits)
     in one fused op, scaled by the GLOBAL batch size so µbatch/DP
     gradients sum to the sequential gradient (layers.py:146-148).
+
+    Training metrics: with an accumulator in `_metrics` (see
+    Sequential.set_metrics) a training-mode backward also adds the
+    µbatch's loss sum, argmax matches and row counts to it
+    (F.head_metrics, one small launch, no host sync).
     """
+
+    kind = None      # "xent" | "mse": the loss F.head_metrics reports
+    _metrics = None  # metrics accumulator, or None (off)
 
     def __init__(self, global_batch_size: int):
         super().__init__()
@@ -399,12 +407,16 @@ class _LossHead(Module):
         s = self._unstash("s", mubatch_id)
         if target.dtype != s.dtype:
             target = target.to(s.dtype)
+        if self._metrics is not None and self._training:
+            F.head_metrics(s, target, self._metrics, self.kind)
         return self._bwd(s, target)
 
 
 class SoftmaxMSE(_LossHead):
     """Softmax → MSE, matching the reference's Softmax+MSELoss pair
     (layers.py:83-96,145-166) as ONE fused head."""
+
+    kind = "mse"
 
     def _bwd(self, probs, target):
         return F.head_softmax_mse_bwd(probs, target, self.global_batch_size)
@@ -413,6 +425,8 @@ class SoftmaxMSE(_LossHead):
 class SoftmaxXent(_LossHead):
     """Fused softmax-cross-entropy head: dz = (s − t)/GB.  The improved
     default loss head (BASELINE.json north star)."""
+
+    kind = "xent"
 
     def _bwd(self, probs, target):
         return F.head_softmax_xent_bwd(probs, target, self.global_batch_size)
@@ -506,10 +520,16 @@ class Sequential(Module):
             target = target.contiguous()
         in_kernel = (F.head_wgrad_fused() and not lin._defer_wgrad
                      and not F.deterministic())
+        # training metrics ride in the same kernel (no second launch)
+        # unless the standalone launch is asked for
+        acc = head._metrics if head._training else None
+        if acc is not None and not F.head_metrics_fused():
+            F.head_metrics(s, target, acc, head.kind)
+            acc = None
         dz, dx = F.head_bwd_fused(
             s, target, x, lin.weight.compute_t(), head.global_batch_size,
             lin.weight.grad if in_kernel else None,
-            lin.bias.grad if in_kernel else None)
+            lin.bias.grad if in_kernel else None, metrics=acc)
         if lin._defer_wgrad:
             lin._wgrad_pending.append((dz, x, None))
             if len(lin._wgrad_pending) >= lin._wgrad_window:
@@ -574,6 +594,16 @@ class Sequential(Module):
         self._training = False
         for l in self.layers:
             l.eval()
+
+    def set_metrics(self, acc):
+        """Point the loss head at a metrics accumulator
+        (F.new_metrics_acc), or at None to stop counting.  Returns True
+        when this chain ends in a loss head."""
+        head = self.layers[-1] if self.layers else None
+        if not isinstance(head, _LossHead):
+            return False
+        head._metrics = acc
+        return True
 
     def set_fp8_fwd(self, flag: bool):
         """Enable the MX-fp8 training forward on every qualifying

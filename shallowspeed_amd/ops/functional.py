@@ -321,22 +321,122 @@ def head_fwd_fused(x, w, b):
 
 
 def head_bwd_fused(probs, target, x, w_t, global_batch, grad_w=None,
-                   grad_b=None):
+                   grad_b=None, metrics=None):
     """(dz, dx) of the fused head in one kernel: dz = (probs - t)/GB,
     dx = dz @ W — bit-identical to head_softmax_xent_bwd ->
     linear_dgrad.  With grad_w (and grad_b) given, the same kernel also
     accumulates grad_w += dz^T @ x and grad_b += colsum(dz) with f32
-    atomics (one set per block, at most 256 blocks)."""
+    atomics (one set per block, at most 256 blocks).  With `metrics` (an
+    accumulator of new_metrics_acc) it also adds the cross-entropy
+    metric totals of (probs, target) — same values as head_metrics, no
+    second launch; dz and dx keep their bits."""
     empty = torch.Tensor()
-    return tuple(_ext_for(probs).head_bwd_fused(
-        probs, target, x, w_t, float(global_batch),
-        grad_w if grad_w is not None else empty,
-        grad_b if grad_b is not None else empty))
+    args = (probs, target, x, w_t, float(global_batch),
+            grad_w if grad_w is not None else empty,
+            grad_b if grad_b is not None else empty)
+    if metrics is None:
+        return tuple(_ext_for(probs).head_bwd_fused(*args))
+    return tuple(_ext_for(probs).head_bwd_fused(*args, 0, metrics, 0))
 
 
 def xent_loss(probs, target, global_batch, eps=1e-9):
     """−Σ t·log(p)/GB (logging only)."""
     return -(target * torch.log(probs.float() + eps)).sum() / global_batch
+
+
+# ------------------------------------------------------- training metrics
+#
+# One definition for every path (GPU kernels in csrc/head.hip, torch on
+# the CPU).  For probs p and target t of shape (M, C), a call adds
+#   rows      += M
+#   nonfinite += rows with any NaN / ±Inf in p (these add nothing below)
+#   loss_sum  += Σ_r −Σ_c t·log(max(p, FLT_MIN))  over t != 0     (xent)
+#                Σ_r Σ_c (t − p)²                                  (mse)
+#   correct   += rows with argmax_c p == argmax_c t, lowest index on ties
+# to an accumulator of S slots x 4 32-bit words (word 0: f32 loss_sum,
+# words 1..3: int32 correct, rows, nonfinite).  A GPU block adds into
+# slot blockIdx % S so a launch's atomics do not queue on one address;
+# the slots are folded on the host, in f64 / int64, at read time only.
+
+METRICS_SLOTS = 16  # the shipped S on GPU (docs/KERNELS.md, head metrics)
+_FLT_MIN = 1.1754943508222875e-38
+
+_HEAD_METRICS_FUSED = None
+
+
+def set_head_metrics_fused(flag: bool):
+    """Let the fused head backward count the training metrics itself
+    (default).  Off: the fused backward runs without them and a
+    head_metrics launch follows — the measured alternative,
+    SS_HEAD_METRICS_FUSED=0 (read once)."""
+    global _HEAD_METRICS_FUSED
+    _HEAD_METRICS_FUSED = bool(flag)
+
+
+def head_metrics_fused() -> bool:
+    global _HEAD_METRICS_FUSED
+    if _HEAD_METRICS_FUSED is None:
+        import os
+
+        _HEAD_METRICS_FUSED = \
+            os.environ.get("SS_HEAD_METRICS_FUSED", "1") != "0"
+    return _HEAD_METRICS_FUSED
+
+
+def new_metrics_acc(device, slots=None):
+    """A zeroed metrics accumulator on `device`.  slots: a power of two;
+    default METRICS_SLOTS on GPU, 1 on CPU."""
+    device = torch.device(device)
+    if slots is None:
+        slots = METRICS_SLOTS if device.type == "cuda" else 1
+    assert slots >= 1 and slots & (slots - 1) == 0, \
+        f"slots must be a power of two, got {slots}"
+    return torch.zeros(slots, 4, dtype=torch.int32, device=device)
+
+
+def head_metrics(probs, target, acc, kind="xent"):
+    """Add the metric totals of (probs, target) to `acc` (definition
+    above).  GPU: one launch of head_metrics_kernel, no host sync."""
+    assert kind in ("xent", "mse"), kind
+    assert probs.dim() == 2 and probs.shape == target.shape, \
+        (probs.shape, target.shape)
+    if _is_gpu(probs):
+        if target.dtype != probs.dtype:
+            target = target.to(probs.dtype)
+        _ext_for(probs).head_metrics(
+            probs if probs.is_contiguous() else probs.contiguous(),
+            target if target.is_contiguous() else target.contiguous(),
+            acc, kind)
+        return
+    p, t = probs.float(), target.float()
+    fin = torch.isfinite(p).all(dim=1)
+    if kind == "xent":
+        logp = torch.log(torch.clamp(p, min=_FLT_MIN))
+        terms = torch.where(t != 0, -t * logp, torch.zeros_like(p))
+    else:
+        terms = (t - p) ** 2
+    loss = terms.sum(dim=1)[fin].double().sum()
+    hit = (p.argmax(dim=1) == t.argmax(dim=1)) & fin
+    acc.view(torch.float32)[0, 0] += loss.float()
+    acc[0, 1] += int(hit.sum())
+    acc[0, 2] += p.shape[0]
+    acc[0, 3] += int((~fin).sum())
+
+
+def read_metrics_acc(acc, reset=True):
+    """Fold the slots on the host (one device-to-host copy, f64 / int64
+    sums) into {loss_sum, correct, rows, nonfinite}; reset=True zeroes
+    the accumulator afterwards."""
+    host = acc.to("cpu", copy=True)
+    if reset:
+        acc.zero_()
+    counts = host[:, 1:].to(torch.int64).sum(dim=0)
+    return {
+        "loss_sum": float(host.view(torch.float32)[:, 0].double().sum()),
+        "correct": int(counts[0]),
+        "rows": int(counts[1]),
+        "nonfinite": int(counts[2]),
+    }
 
 
 # ----------------------------------------------- layernorm / gelu (extras)

@@ -52,7 +52,7 @@ class _BatchedP2P:
 
 class Worker:
     def __init__(self, topo: Topology, model, dataset=None, optimizer=None,
-                 use_dp: bool = True, bucket_bytes=None):
+                 use_dp: bool = True, bucket_bytes=None, metrics=None):
         self.topo = topo
         self.model = model
         self.dataset = dataset
@@ -71,6 +71,15 @@ class Worker:
         self.comm_stats = {}         # p2p overlap counters (debug/timing)
         self._timing = False
 
+        # training metrics (loss / accuracy / non-finite rows, counted
+        # on device by the loss head).  None = SS_TRAIN_METRICS (default
+        # off), so a benchmark run can price them from the environment.
+        # Allocated here, before any graph capture can bake addresses.
+        self._metrics_acc = None
+        if metrics is None:
+            metrics = os.environ.get("SS_TRAIN_METRICS", "0") == "1"
+        self.set_metrics(metrics)
+
         self._DISPATCH = {
             ZeroGrad: self._zero_grad,
             OptimizerStep: self._optimizer_step,
@@ -84,6 +93,58 @@ class Worker:
             BackwardGradAcc: self._backward_acc,
             BackwardGradAllReduce: self._backward_and_reduce,
         }
+
+    # ------------------------------------------------------------ metrics
+    def set_metrics(self, on: bool):
+        """Turn the training metrics on or off.  Only a last-stage
+        training worker (one with an optimizer) counts; elsewhere this
+        is a no-op.  Captured graphs hold the old kernel sequence, so a
+        change drops them."""
+        from ..ops import functional as F
+
+        want = (bool(on) and self.optimizer is not None
+                and self.topo.stage_id == self.topo.pp - 1
+                and hasattr(self.model, "set_metrics"))
+        if want == (self._metrics_acc is not None):
+            return
+        acc = F.new_metrics_acc(self.device) if want else None
+        if want and not self.model.set_metrics(acc):
+            return  # the chain has no loss head
+        if not want:
+            self.model.set_metrics(None)
+        self._metrics_acc = acc
+        if hasattr(self, "_graphs"):
+            self._graphs = {}
+
+    def read_metrics(self, reset: bool = True):
+        """Totals since the last reset, summed over the DP group:
+        {loss_sum, correct, rows, nonfinite, loss, acc} with
+        loss = loss_sum / (rows - nonfinite) and acc = correct / rows.
+        One device-to-host copy (and one small all-reduce under DP);
+        call it per epoch or logging interval, not per step.  Returns
+        None, and calls no collective, on a worker that does not count
+        (non-last stage, no optimizer, metrics off).  TP ranks hold a
+        replicated head, so nothing is reduced over TP."""
+        if self._metrics_acc is None:
+            return None
+        from ..ops import functional as F
+
+        m = F.read_metrics_acc(self._metrics_acc, reset=reset)
+        if self.topo.dp > 1:
+            import torch.distributed as dist
+
+            t = torch.tensor([m["loss_sum"], m["correct"], m["rows"],
+                              m["nonfinite"]], dtype=torch.float64)
+            if self.device.type == "cuda":
+                t = t.to(self.device)
+            dist.all_reduce(t, group=self.topo.dp_group)
+            t = t.cpu()
+            m = {"loss_sum": float(t[0]), "correct": int(t[1]),
+                 "rows": int(t[2]), "nonfinite": int(t[3])}
+        good = m["rows"] - m["nonfinite"]
+        m["loss"] = m["loss_sum"] / good if good > 0 else float("nan")
+        m["acc"] = m["correct"] / m["rows"] if m["rows"] > 0 else float("nan")
+        return m
 
     # ------------------------------------------------------------ buffers
     def _ensure_buffers(self, num_buffers: int, mubatch_size: int):

@@ -15,6 +15,7 @@ Single process: python train.py          (dp=1, pp=1, CPU or 1 GPU)
 """
 
 import argparse
+import sys
 import time
 
 import torch
@@ -25,36 +26,48 @@ from shallowspeed_amd.parallel import SCHEDULES, InferenceSchedule, Worker, init
 from shallowspeed_amd.utils import assert_sync, get_model_hash, rprint
 
 
-def compute_accuracy(model, worker, dataset, topo):
-    """Forward-only eval over the val split; returns accuracy on the
-    last stage, None elsewhere.  Reference: train.py:21-47 (argmax of
-    the output buffer vs argmax of target, train.py:40-43)."""
+def compute_val_metrics(model, worker, dataset, topo, kind="xent"):
+    """Forward-only eval over the val split; returns {acc, loss, ...} on
+    the last stage, None elsewhere.  Reference: train.py:21-47 (argmax
+    of the output buffer vs argmax of target, train.py:40-43).  One
+    F.head_metrics launch per batch on the output buffer, one read at
+    the end — no per-batch host sync."""
+    from shallowspeed_amd.ops import functional as F
+
     model.eval()
-    correct, total = 0, 0
+    last = topo.stage_id == topo.pp - 1
+    acc_buf = F.new_metrics_acc(topo.device) if last else None
     sched = InferenceSchedule(1, topo.pp, topo.stage_id)
     for b in range(dataset.num_batches()):
         worker.execute(sched, b)
-        if topo.stage_id == topo.pp - 1:
-            from shallowspeed_amd.ops.functional import row_argmax
-
+        if last:
             probs = worker._out_bufs[0]
             target = dataset.micro_batch_target(b, 0)
-            pred = row_argmax(probs)
-            lab = row_argmax(target.to(probs.device))
-            correct += (pred == lab).sum().item()
-            total += pred.numel()
+            F.head_metrics(probs, target.to(probs.device), acc_buf, kind)
     model.train()
-    if topo.stage_id != topo.pp - 1:
+    if not last:
         return None
+    m = F.read_metrics_acc(acc_buf, reset=False)
     if topo.dp > 1:
-        t = torch.tensor([correct, total], dtype=torch.float64)
+        t = torch.tensor([m["loss_sum"], m["correct"], m["rows"],
+                          m["nonfinite"]], dtype=torch.float64)
         import torch.distributed as dist
 
         if topo.device.type == "cuda":
             t = t.to(topo.device)
         dist.all_reduce(t, group=topo.dp_group)
-        correct, total = t[0].item(), t[1].item()
-    return correct / max(total, 1)
+        t = t.cpu()
+        m = {"loss_sum": float(t[0]), "correct": int(t[1]),
+             "rows": int(t[2]), "nonfinite": int(t[3])}
+    m["acc"] = m["correct"] / max(m["rows"], 1)
+    m["loss"] = m["loss_sum"] / max(m["rows"] - m["nonfinite"], 1)
+    return m
+
+
+def compute_accuracy(model, worker, dataset, topo):
+    """Validation accuracy on the last stage, None elsewhere."""
+    m = compute_val_metrics(model, worker, dataset, topo)
+    return None if m is None else m["acc"]
 
 
 def parse_sizes(s):
@@ -117,6 +130,13 @@ def main():
     ap.add_argument("--timing", action="store_true",
                     help="print per-instruction wall time after training")
     ap.add_argument("--resume", default=None, help="checkpoint dir to read")
+    ap.add_argument("--no-metrics", action="store_true",
+                    help="do not count training loss / accuracy / "
+                         "non-finite rows on device (the epoch line then "
+                         "has val_acc and val_loss only)")
+    ap.add_argument("--halt-on-nonfinite", action="store_true",
+                    help="exit with status 3 after an epoch whose training "
+                         "metrics saw a row with NaN/Inf probabilities")
     args = ap.parse_args()
 
     assert args.global_batch % (args.dp * args.mubatches) == 0, \
@@ -187,7 +207,8 @@ def main():
                      n_classes=args.layer_sizes[-1], device=device)
     val_ds.load(topo.dp_rank, args.dp)
 
-    worker = Worker(topo, model, train_ds, optimizer)
+    worker = Worker(topo, model, train_ds, optimizer,
+                    metrics=not args.no_metrics)
     if args.timing:
         worker.enable_instruction_timing(True)
     val_worker = Worker(topo, model, val_ds, None, use_dp=False)
@@ -212,16 +233,29 @@ def main():
     for epoch in range(args.epochs):
         t0 = time.time()
         optimizer.lr = lr_at(epoch)
-        acc = compute_accuracy(model, val_worker, val_ds, topo)
+        val = compute_val_metrics(model, val_worker, val_ds, topo, args.loss)
         for batch_id in range(train_ds.num_batches()):
             sched = sched_cls(train_ds.num_mubatches(), args.pp, topo.stage_id)
             worker.execute(sched, batch_id)
         if device.type == "cuda":
             torch.cuda.synchronize(device)
+        # one read per epoch; every last-stage DP rank takes part in
+        # the reduction, other stages get None
+        tm = worker.read_metrics(reset=True)
         if topo.stage_id == topo.pp - 1 and topo.dp_rank == 0 \
                 and (topo.tp == 1 or topo.tp_rank == 0):
-            print(f"epoch {epoch:3d}  val_acc={acc:.4f}  "
-                  f"time={time.time()-t0:.2f}s", flush=True)
+            line = (f"epoch {epoch:3d}  val_acc={val['acc']:.4f}  "
+                    f"val_loss={val['loss']:.4f}  ")
+            if tm is not None:
+                line += (f"train_loss={tm['loss']:.4f}  "
+                         f"train_acc={tm['acc']:.4f}  ")
+            print(line + f"time={time.time()-t0:.2f}s", flush=True)
+            if tm is not None and tm["nonfinite"] > 0:
+                print(f"WARNING: {tm['nonfinite']} non-finite rows",
+                      flush=True)
+        if args.halt_on_nonfinite and tm is not None \
+                and tm["nonfinite"] > 0:
+            sys.exit(3)
 
     acc = compute_accuracy(model, val_worker, val_ds, topo)
     if topo.stage_id == topo.pp - 1 and topo.dp_rank == 0 \
