@@ -1,76 +1,18 @@
 // Python bindings for the shallowspeed_amd HIP/CDNA4 kernels.
 //
 // Thin torch-extension layer: shape/dtype/contiguity checks + launch on
-// the current torch stream.  All compute lives in gemm.hip /
-// elementwise.hip (raw HIP, extern "C" launchers).
+// the current torch stream.  All compute lives in the .hip files, behind
+// the launchers declared in launchers.h.
 
 #include <torch/extension.h>
 
 #include <ATen/cuda/CUDAContext.h>
-#include <hip/hip_runtime.h>
 
 #include <climits>
 #include <optional>
 #include <string>
 
-extern "C" {
-void ss_gemm_nt(const void*, const void*, const void*, const void*, void*,
-                int, int, int, bool, hipStream_t);
-void ss_wgrad_tn(const void*, const void*, const void*, void*, void*, int,
-                 int, int, int, hipStream_t);
-void ss_wgrad_tn_multi(const void*, int, bool, void*, void*, int, int, int,
-                       int, hipStream_t);
-void ss_colsum(const void*, const void*, void*, int, int, hipStream_t);
-void ss_relu_fwd(const void*, void*, long, hipStream_t);
-void ss_relu_bwd(const void*, const void*, void*, long, hipStream_t);
-void ss_softmax_fwd(const void*, void*, int, int, hipStream_t);
-void ss_softmax_bwd(const void*, const void*, void*, int, int, hipStream_t);
-void ss_head_mse_bwd(const void*, const void*, void*, int, int, float,
-                     hipStream_t);
-void ss_head_xent_bwd(const void*, const void*, void*, long, float,
-                      hipStream_t);
-void ss_transpose_bf16(const void*, void*, int, int, hipStream_t);
-void ss_sgd_multi2(const void*, const void*, int, float, float, float,
-                   hipStream_t);
-void ss_adamw_multi2(const void*, const void*, int, float, float, float,
-                     float, float, float, float, hipStream_t);
-void ss_adamw_multi(const void*, int, long, float, float, float, float,
-                    float, float, float, hipStream_t);
-void ss_sgd_multi(const void*, int, long, float, float, float,
-                  hipStream_t);
-void ss_ln_fwd(const void*, const void*, const void*, void*, void*, void*,
-               int, int, float, hipStream_t);
-void ss_ln_bwd_dx(const void*, const void*, const void*, const void*,
-                  const void*, void*, int, int, hipStream_t);
-void ss_ln_bwd_dparam(const void*, const void*, const void*, const void*,
-                      void*, void*, int, int, hipStream_t);
-void ss_gelu_fwd(const void*, void*, long, hipStream_t);
-void ss_gelu_bwd(const void*, const void*, void*, long, hipStream_t);
-void ss_row_argmax(const void*, void*, int, int, hipStream_t);
-}
-// C++-linkage (gemm256.hip / wgrad256.hip / fused_mlp.hip)
-bool ss_fused_mlp_fwd(const void*, const void*, int, int, int, int, void*,
-                      hipStream_t);
-bool ss_gemm_nt_256w(const void*, const void*, const void*, void*, int, int,
-                     int, bool, hipStream_t);
-bool ss_gemm_nt_256(const void*, const void*, const void*, void*, int, int,
-                    int, bool, hipStream_t);
-bool ss_wgrad_tn_256(const void*, const void*, void*, int, int, int,
-                     hipStream_t);
-void ss_fp8_quantize(const void*, void*, void*, int, int, hipStream_t);
-bool ss_gemm_nt_f8(const void*, const void*, const void*, const void*,
-                   const void*, void*, int, int, int, bool, hipStream_t);
-bool ss_gemm_nt_f8_q(const void*, const void*, const void*, const void*,
-                     const void*, void*, void*, int, int, int, bool,
-                     hipStream_t);
-// head.hip
-bool ss_head_fwd_fused(const void*, const void*, const void*, void*, int, int,
-                       int, int, hipStream_t);
-bool ss_head_bwd_fused(const void*, const void*, const void*, const void*,
-                       void*, void*, void*, void*, int, int, int, float, int,
-                       void*, int, hipStream_t);
-bool ss_head_metrics(const void*, const void*, void*, int, int, int, int,
-                     hipStream_t);
+#include "launchers.h"
 
 namespace {
 
@@ -92,6 +34,27 @@ void check_f32(const torch::Tensor& t, const char* name) {
 
 bool has(const torch::Tensor& t) { return t.defined() && t.numel() > 0; }
 
+// Optional tensor: null when absent, else checked and its data pointer.
+void* opt_bf16(const torch::Tensor& t, const char* name) {
+    if (!has(t)) return nullptr;
+    check_bf16(t, name);
+    return t.data_ptr();
+}
+
+void* opt_f32(const torch::Tensor& t, const char* name) {
+    if (!has(t)) return nullptr;
+    check_f32(t, name);
+    return t.data_ptr();
+}
+
+// int64 CUDA table of `cols` columns (descriptor rows holding pointers
+// and sizes); `what` is the error text.
+void check_table(const torch::Tensor& t, int64_t cols, const char* what) {
+    TORCH_CHECK(t.is_cuda() && t.scalar_type() == torch::kLong &&
+                    t.is_contiguous() && t.dim() == 2 && t.size(1) == cols,
+                what);
+}
+
 torch::Tensor gemm_nt(torch::Tensor a, torch::Tensor b, torch::Tensor bias,
                       torch::Tensor mask, bool relu) {
     check_bf16(a, "a");
@@ -99,58 +62,40 @@ torch::Tensor gemm_nt(torch::Tensor a, torch::Tensor b, torch::Tensor bias,
     TORCH_CHECK(a.dim() == 2 && b.dim() == 2, "a/b must be 2-D");
     const int M = a.size(0), K = a.size(1), N = b.size(0);
     TORCH_CHECK(b.size(1) == K, "K mismatch: ", K, " vs ", b.size(1));
-    const void* bias_p = nullptr;
-    if (has(bias)) {
-        check_bf16(bias, "bias");
-        TORCH_CHECK(bias.numel() == N, "bias size");
-        bias_p = bias.data_ptr();
-    }
-    const void* mask_p = nullptr;
-    if (has(mask)) {
-        check_bf16(mask, "mask");
-        TORCH_CHECK(mask.sizes() == a.sizes(), "mask must match A");
-        mask_p = mask.data_ptr();
-    }
+    const void* bias_p = opt_bf16(bias, "bias");
+    TORCH_CHECK(!bias_p || bias.numel() == N, "bias size");
+    const void* mask_p = opt_bf16(mask, "mask");
+    TORCH_CHECK(!mask_p || mask.sizes() == a.sizes(), "mask must match A");
     auto c = torch::empty({M, N}, a.options());
     ss_gemm_nt(a.data_ptr(), b.data_ptr(), bias_p, mask_p, c.data_ptr(), M, N,
                K, relu, cur_stream());
     return c;
 }
 
-torch::Tensor gemm_nt_256(torch::Tensor a, torch::Tensor b,
-                          torch::Tensor bias, bool relu) {
+// shared body of the two 256-tile wrappers; `tier` names it in the error
+torch::Tensor gemm_nt_256_tier(decltype(&ss_gemm_nt_256) launcher,
+                               const char* tier, const torch::Tensor& a,
+                               const torch::Tensor& b,
+                               const torch::Tensor& bias, bool relu) {
     check_bf16(a, "a");
     check_bf16(b, "b");
     const int M = a.size(0), K = a.size(1), N = b.size(0);
     TORCH_CHECK(b.size(1) == K, "K mismatch");
-    const void* bias_p = nullptr;
-    if (has(bias)) {
-        check_bf16(bias, "bias");
-        bias_p = bias.data_ptr();
-    }
     auto c = torch::empty({M, N}, a.options());
-    TORCH_CHECK(ss_gemm_nt_256(a.data_ptr(), b.data_ptr(), bias_p,
-                               c.data_ptr(), M, N, K, relu, cur_stream()),
-                "shape outside the 256-tile tier: ", M, "x", N, "x", K);
+    TORCH_CHECK(launcher(a.data_ptr(), b.data_ptr(), opt_bf16(bias, "bias"),
+                         c.data_ptr(), M, N, K, relu, cur_stream()),
+                "shape outside the ", tier, " tier: ", M, "x", N, "x", K);
     return c;
+}
+
+torch::Tensor gemm_nt_256(torch::Tensor a, torch::Tensor b,
+                          torch::Tensor bias, bool relu) {
+    return gemm_nt_256_tier(&ss_gemm_nt_256, "256-tile", a, b, bias, relu);
 }
 
 torch::Tensor gemm_nt_256w(torch::Tensor a, torch::Tensor b,
                            torch::Tensor bias, bool relu) {
-    check_bf16(a, "a");
-    check_bf16(b, "b");
-    const int M = a.size(0), K = a.size(1), N = b.size(0);
-    TORCH_CHECK(b.size(1) == K, "K mismatch");
-    const void* bias_p = nullptr;
-    if (has(bias)) {
-        check_bf16(bias, "bias");
-        bias_p = bias.data_ptr();
-    }
-    auto c = torch::empty({M, N}, a.options());
-    TORCH_CHECK(ss_gemm_nt_256w(a.data_ptr(), b.data_ptr(), bias_p,
-                                c.data_ptr(), M, N, K, relu, cur_stream()),
-                "shape outside the 256w tier: ", M, "x", N, "x", K);
-    return c;
+    return gemm_nt_256_tier(&ss_gemm_nt_256w, "256w", a, b, bias, relu);
 }
 
 std::vector<torch::Tensor> fp8_quantize(torch::Tensor x) {
@@ -165,47 +110,49 @@ std::vector<torch::Tensor> fp8_quantize(torch::Tensor x) {
     return {q, s};
 }
 
-torch::Tensor gemm_nt_f8(torch::Tensor a, torch::Tensor asc, torch::Tensor b,
-                         torch::Tensor bsc, torch::Tensor bias, bool relu) {
+// shared body of the two fp8 GEMM wrappers: bf16 output C, or with
+// quantized = true the fused-quantised pair (e4m3 data, e8m0 scales)
+std::vector<torch::Tensor> gemm_nt_f8_any(bool quantized,
+                                          const torch::Tensor& a,
+                                          const torch::Tensor& asc,
+                                          const torch::Tensor& b,
+                                          const torch::Tensor& bsc,
+                                          const torch::Tensor& bias,
+                                          bool relu) {
     TORCH_CHECK(a.scalar_type() == torch::kUInt8 &&
                 b.scalar_type() == torch::kUInt8, "a/b must be u8 (e4m3)");
     TORCH_CHECK(a.is_contiguous() && b.is_contiguous() &&
                 asc.is_contiguous() && bsc.is_contiguous(), "contiguous");
     const int M = a.size(0), K = a.size(1), N = b.size(0);
     TORCH_CHECK(b.size(1) == K, "K mismatch");
-    const void* bias_p = nullptr;
-    if (has(bias)) {
-        check_bf16(bias, "bias");
-        bias_p = bias.data_ptr();
+    const void* bias_p = opt_bf16(bias, "bias");
+    std::vector<torch::Tensor> out;
+    bool ok;
+    if (quantized) {
+        out = {torch::empty({M, N}, a.options()),
+               torch::empty({N / 128, M, 4}, a.options())};
+        ok = ss_gemm_nt_f8_q(a.data_ptr(), asc.data_ptr(), b.data_ptr(),
+                             bsc.data_ptr(), bias_p, out[0].data_ptr(),
+                             out[1].data_ptr(), M, N, K, relu, cur_stream());
+    } else {
+        out = {torch::empty({M, N}, a.options().dtype(torch::kBFloat16))};
+        ok = ss_gemm_nt_f8(a.data_ptr(), asc.data_ptr(), b.data_ptr(),
+                           bsc.data_ptr(), bias_p, out[0].data_ptr(), M, N, K,
+                           relu, cur_stream());
     }
-    auto c = torch::empty({M, N},
-                          a.options().dtype(torch::kBFloat16));
-    TORCH_CHECK(ss_gemm_nt_f8(a.data_ptr(), asc.data_ptr(), b.data_ptr(),
-                              bsc.data_ptr(), bias_p, c.data_ptr(), M, N, K,
-                              relu, cur_stream()),
-                "shape outside the fp8 tier: ", M, "x", N, "x", K);
-    return c;
+    TORCH_CHECK(ok, "shape outside the fp8 tier: ", M, "x", N, "x", K);
+    return out;
+}
+
+torch::Tensor gemm_nt_f8(torch::Tensor a, torch::Tensor asc, torch::Tensor b,
+                         torch::Tensor bsc, torch::Tensor bias, bool relu) {
+    return gemm_nt_f8_any(false, a, asc, b, bsc, bias, relu)[0];
 }
 
 std::vector<torch::Tensor> gemm_nt_f8_q(torch::Tensor a, torch::Tensor asc,
                                          torch::Tensor b, torch::Tensor bsc,
                                          torch::Tensor bias, bool relu) {
-    TORCH_CHECK(a.scalar_type() == torch::kUInt8 &&
-                b.scalar_type() == torch::kUInt8, "a/b must be u8 (e4m3)");
-    const int M = a.size(0), K = a.size(1), N = b.size(0);
-    TORCH_CHECK(b.size(1) == K, "K mismatch");
-    const void* bias_p = nullptr;
-    if (has(bias)) {
-        check_bf16(bias, "bias");
-        bias_p = bias.data_ptr();
-    }
-    auto cq = torch::empty({M, N}, a.options());
-    auto cs = torch::empty({N / 128, M, 4}, a.options());
-    TORCH_CHECK(ss_gemm_nt_f8_q(a.data_ptr(), asc.data_ptr(), b.data_ptr(),
-                                bsc.data_ptr(), bias_p, cq.data_ptr(),
-                                cs.data_ptr(), M, N, K, relu, cur_stream()),
-                "shape outside the fp8 tier: ", M, "x", N, "x", K);
-    return {cq, cs};
+    return gemm_nt_f8_any(true, a, asc, b, bsc, bias, relu);
 }
 
 void wgrad_tn_256(torch::Tensor dy, torch::Tensor x, torch::Tensor gw) {
@@ -228,18 +175,10 @@ void wgrad_tn(torch::Tensor dy, torch::Tensor x, torch::Tensor gw,
     const int Kb = dy.size(0), Mo = dy.size(1), N = x.size(1);
     TORCH_CHECK(x.size(0) == Kb, "batch mismatch");
     TORCH_CHECK(gw.size(0) == Mo && gw.size(1) == N, "gw shape");
-    const void* mask_p = nullptr;
-    if (has(mask)) {
-        check_bf16(mask, "mask");
-        TORCH_CHECK(mask.sizes() == dy.sizes(), "mask must match dy");
-        mask_p = mask.data_ptr();
-    }
-    void* gb_p = nullptr;
-    if (has(gb)) {
-        check_f32(gb, "gb");
-        TORCH_CHECK(gb.numel() == Mo, "gb size");
-        gb_p = gb.data_ptr();
-    }
+    const void* mask_p = opt_bf16(mask, "mask");
+    TORCH_CHECK(!mask_p || mask.sizes() == dy.sizes(), "mask must match dy");
+    void* gb_p = opt_f32(gb, "gb");
+    TORCH_CHECK(!gb_p || gb.numel() == Mo, "gb size");
     // bias grad is FUSED into the wgrad kernel (n-tile-0 blocks sum
     // the already-masked LDS dY tile) — no separate colsum launch or
     // extra dY read on the hot path.
@@ -254,20 +193,13 @@ void wgrad_tn_multi(torch::Tensor chunk_table, int64_t nchunks,
     // chunk_table: CUDA int64 [nchunks, 3] = {dY*, X*, mask*} per
     // µbatch; all chunks share (Kb, Mo, N).  Deferred-µbatch wgrad:
     // one launch accumulates every chunk into gw/gb.
-    TORCH_CHECK(chunk_table.is_cuda() &&
-                    chunk_table.scalar_type() == torch::kLong &&
-                    chunk_table.is_contiguous() &&
-                    chunk_table.dim() == 2 && chunk_table.size(1) == 3 &&
-                    chunk_table.size(0) == nchunks,
+    check_table(chunk_table, 3, "chunk_table must be CUDA int64 [nchunks,3]");
+    TORCH_CHECK(chunk_table.size(0) == nchunks,
                 "chunk_table must be CUDA int64 [nchunks,3]");
     check_f32(gw, "gw");
     TORCH_CHECK(gw.size(0) == Mo && gw.size(1) == N, "gw shape");
-    void* gb_p = nullptr;
-    if (has(gb)) {
-        check_f32(gb, "gb");
-        TORCH_CHECK(gb.numel() == Mo, "gb size");
-        gb_p = gb.data_ptr();
-    }
+    void* gb_p = opt_f32(gb, "gb");
+    TORCH_CHECK(!gb_p || gb.numel() == Mo, "gb size");
     ss_wgrad_tn_multi(chunk_table.data_ptr(), (int)nchunks, has_mask,
                       gw.data_ptr(), gb_p, (int)Mo, (int)N, (int)kb_chunk,
                       (int)split_k, cur_stream());
@@ -275,11 +207,7 @@ void wgrad_tn_multi(torch::Tensor chunk_table, int64_t nchunks,
 
 torch::Tensor colsum(torch::Tensor dy, torch::Tensor mask) {
     check_bf16(dy, "dy");
-    const void* mask_p = nullptr;
-    if (has(mask)) {
-        check_bf16(mask, "mask");
-        mask_p = mask.data_ptr();
-    }
+    const void* mask_p = opt_bf16(mask, "mask");
     auto gb = torch::zeros({dy.size(1)},
                            dy.options().dtype(torch::kFloat));
     ss_colsum(dy.data_ptr(), mask_p, gb.data_ptr(), dy.size(0), dy.size(1),
@@ -409,21 +337,12 @@ std::vector<torch::Tensor> head_bwd_fused(torch::Tensor probs,
     TORCH_CHECK(probs.size(0) == M, "batch mismatch");
     TORCH_CHECK(w_t.size(0) == K && w_t.size(1) == C, "w_t must be [K][C]");
     check_align16(x, "x");
-    void* gw_p = nullptr;
-    void* gb_p = nullptr;
-    if (has(grad_w)) {
-        check_f32(grad_w, "grad_w");
-        TORCH_CHECK(grad_w.dim() == 2 && grad_w.size(0) == C &&
-                        grad_w.size(1) == K, "grad_w shape");
-        gw_p = grad_w.data_ptr();
-        if (has(grad_b)) {
-            check_f32(grad_b, "grad_b");
-            TORCH_CHECK(grad_b.numel() == C, "grad_b size");
-            gb_p = grad_b.data_ptr();
-        }
-    } else {
-        TORCH_CHECK(!has(grad_b), "grad_b given without grad_w");
-    }
+    void* gw_p = opt_f32(grad_w, "grad_w");
+    TORCH_CHECK(!gw_p || (grad_w.dim() == 2 && grad_w.size(0) == C &&
+                          grad_w.size(1) == K), "grad_w shape");
+    TORCH_CHECK(gw_p || !has(grad_b), "grad_b given without grad_w");
+    void* gb_p = opt_f32(grad_b, "grad_b");
+    TORCH_CHECK(!gb_p || grad_b.numel() == C, "grad_b size");
     // metrics: the kernel also adds the batch's metric totals into this
     // accumulator, using its first `slots` slots (0 = all of them)
     void* met_p = nullptr;
@@ -543,10 +462,7 @@ torch::Tensor row_argmax(torch::Tensor x) {
 void sgd_multi(torch::Tensor desc, double lr, int64_t total,
                double momentum, double weight_decay) {
     // total passed by the caller (cached host-side) — no device sync.
-    TORCH_CHECK(desc.is_cuda() && desc.scalar_type() == torch::kLong &&
-                    desc.is_contiguous() && desc.dim() == 2 &&
-                    desc.size(1) == 8,
-                "desc must be CUDA int64 [T,8]");
+    check_table(desc, 8, "desc must be CUDA int64 [T,8]");
     ss_sgd_multi(desc.data_ptr(), (int)desc.size(0), (long)total, (float)lr,
                  (float)momentum, (float)weight_decay, cur_stream());
 }
@@ -554,10 +470,7 @@ void sgd_multi(torch::Tensor desc, double lr, int64_t total,
 void adamw_multi(torch::Tensor desc, double lr, int64_t total, double beta1,
                  double beta2, double eps, double weight_decay,
                  double inv_bc1, double inv_bc2) {
-    TORCH_CHECK(desc.is_cuda() && desc.scalar_type() == torch::kLong &&
-                    desc.is_contiguous() && desc.dim() == 2 &&
-                    desc.size(1) == 9,
-                "desc must be CUDA int64 [T,9]");
+    check_table(desc, 9, "desc must be CUDA int64 [T,9]");
     ss_adamw_multi(desc.data_ptr(), (int)desc.size(0), (long)total,
                    (float)lr, (float)beta1, (float)beta2, (float)eps,
                    (float)weight_decay, (float)inv_bc1, (float)inv_bc2,
@@ -566,14 +479,8 @@ void adamw_multi(torch::Tensor desc, double lr, int64_t total, double beta1,
 
 void sgd_multi2(torch::Tensor desc, torch::Tensor bmap, double lr,
                 double momentum, double weight_decay) {
-    TORCH_CHECK(desc.is_cuda() && desc.scalar_type() == torch::kLong &&
-                    desc.is_contiguous() && desc.dim() == 2 &&
-                    desc.size(1) == 8,
-                "desc must be CUDA int64 [T,8]");
-    TORCH_CHECK(bmap.is_cuda() && bmap.scalar_type() == torch::kLong &&
-                    bmap.is_contiguous() && bmap.dim() == 2 &&
-                    bmap.size(1) == 2,
-                "bmap must be CUDA int64 [B,2]");
+    check_table(desc, 8, "desc must be CUDA int64 [T,8]");
+    check_table(bmap, 2, "bmap must be CUDA int64 [B,2]");
     ss_sgd_multi2(desc.data_ptr(), bmap.data_ptr(), (int)bmap.size(0),
                   (float)lr, (float)momentum, (float)weight_decay,
                   cur_stream());
@@ -582,14 +489,8 @@ void sgd_multi2(torch::Tensor desc, torch::Tensor bmap, double lr,
 void adamw_multi2(torch::Tensor desc, torch::Tensor bmap, double lr,
                   double beta1, double beta2, double eps,
                   double weight_decay, double inv_bc1, double inv_bc2) {
-    TORCH_CHECK(desc.is_cuda() && desc.scalar_type() == torch::kLong &&
-                    desc.is_contiguous() && desc.dim() == 2 &&
-                    desc.size(1) == 9,
-                "desc must be CUDA int64 [T,9]");
-    TORCH_CHECK(bmap.is_cuda() && bmap.scalar_type() == torch::kLong &&
-                    bmap.is_contiguous() && bmap.dim() == 2 &&
-                    bmap.size(1) == 2,
-                "bmap must be CUDA int64 [B,2]");
+    check_table(desc, 9, "desc must be CUDA int64 [T,9]");
+    check_table(bmap, 2, "bmap must be CUDA int64 [B,2]");
     ss_adamw_multi2(desc.data_ptr(), bmap.data_ptr(), (int)bmap.size(0),
                     (float)lr, (float)beta1, (float)beta2, (float)eps,
                     (float)weight_decay, (float)inv_bc1, (float)inv_bc2,

@@ -18,6 +18,7 @@
 // Guideline 13), f32 math internally, wave-shuffle row reductions.
 
 #include "common.h"
+#include "launchers.h"
 
 // ------------------------------------------------------------- relu
 
@@ -64,20 +65,6 @@ __global__ __launch_bounds__(256) void relu_bwd_kernel(
 }
 
 // ------------------------------------------------------- row reductions
-
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1)
-        v = fmaxf(v, __shfl_xor(v, off, 64));
-    return v;
-}
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1)
-        v += __shfl_xor(v, off, 64);
-    return v;
-}
 
 // one wave per row; 4 rows per block
 __global__ __launch_bounds__(256) void softmax_fwd_kernel(
@@ -237,15 +224,6 @@ __global__ __launch_bounds__(256) void sgd_multi_kernel(
 
 // ---------------------------------------------------------------- launchers
 
-extern "C" {
-
-static inline int ew_grid(long n) {
-    long blocks = (n / 8 + 255) / 256;
-    if (blocks < 1) blocks = 1;
-    if (blocks > 2048) blocks = 2048;  // grid-stride the rest (G11)
-    return (int)blocks;
-}
-
 void ss_relu_fwd(const void* x, void* y, long n, hipStream_t st) {
     hipLaunchKernelGGL(relu_fwd_kernel, dim3(ew_grid(n)), dim3(256), 0, st,
                        (const __bf16*)x, (__bf16*)y, n);
@@ -286,6 +264,9 @@ void ss_row_argmax(const void* x, void* out, int B, int C, hipStream_t st) {
     hipLaunchKernelGGL(row_argmax_kernel, dim3(cdiv(B, 4)), dim3(256), 0, st,
                        (const __bf16*)x, (int*)out, B, C);
 }
+
+// The kernels below keep the unmangled names that profiles refer to.
+extern "C" {
 
 // ---- blockmap fused optimizers ------------------------------------
 // v2 of the fused optimizer kernels: a host-precomputed block→(tensor,
@@ -532,6 +513,8 @@ __global__ __launch_bounds__(256) void adamw_multi_kernel(
     }
 }
 
+}  // extern "C"
+
 void ss_sgd_multi2(const void* desc, const void* bmap, int nblocks,
                    float lr, float momentum, float weight_decay,
                    hipStream_t st) {
@@ -574,5 +557,3 @@ void ss_sgd_multi(const void* desc, int ntensors, long total, float lr,
                        (const long*)desc, ntensors, total, lr, momentum,
                        weight_decay);
 }
-
-}  // extern "C"

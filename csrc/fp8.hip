@@ -24,17 +24,11 @@
 // serving/inference precision mode; the bench contract stays bf16.
 
 #include "common.h"
+#include "launchers.h"
 
 namespace {
 
-typedef __attribute__((address_space(1))) const unsigned int* gptr_t;
-typedef __attribute__((address_space(3))) unsigned int* lptr_t;
-
 using i32x8 = __attribute__((ext_vector_type(8))) int;
-
-#define SS_VMCNT(n) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(n))
-#define SS_LGKM(n) asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(n))
-#define SS_BAR() __builtin_amdgcn_s_barrier()
 
 // ---------------------------------------------------------------- quant
 
@@ -102,9 +96,7 @@ __global__ __launch_bounds__(512, 1) void gemm_nt_f8_kernel(
     const int gx = gridDim.x, gy = gridDim.y;
     const int nwg = gx * gy;
     const int hw = blockIdx.x + gx * blockIdx.y;
-    const int xcd = hw % 8, q8 = nwg / 8, r8 = nwg % 8;
-    const int wid = (xcd < r8 ? xcd * (q8 + 1)
-                              : r8 * (q8 + 1) + (xcd - r8) * q8) + hw / 8;
+    const int wid = xcd_remap(hw, nwg);
     const int m0 = ((wid / gy) % gx) * 256;
     const int n0 = (wid % gy) * 256;
 
@@ -418,26 +410,32 @@ void ss_fp8_quantize(const void* X, void* Q, void* S, int R, int K,
                        (unsigned char*)S, R, K);
 }
 
+// C (bf16) or, with Cq / Cs given instead, the fused-quantised output
+static bool launch_gemm_f8(const void* A, const void* Asc, const void* B,
+                           const void* Bsc, const void* bias, void* C,
+                           void* Cq, void* Cs, int M, int N, int K, bool relu,
+                           hipStream_t stream) {
+    if (M % 256 || N % 256 || K % 256 || K < 256) return false;
+    if ((long)M * K >= (1L << 31) || (long)N * K >= (1L << 31)) return false;
+    with_bools(
+        [&](auto hb, auto rl, auto emit_q) {
+            hipLaunchKernelGGL(
+                (gemm_nt_f8_kernel<hb.value, rl.value, emit_q.value>),
+                dim3(M / 256, N / 256), dim3(512), 0, stream,
+                (const unsigned char*)A, (const unsigned char*)Asc,
+                (const unsigned char*)B, (const unsigned char*)Bsc,
+                (const __bf16*)bias, (__bf16*)C, (unsigned char*)Cq,
+                (unsigned char*)Cs, M, N, K);
+        },
+        bias != nullptr, relu, Cq != nullptr);
+    return true;
+}
+
 bool ss_gemm_nt_f8(const void* A, const void* Asc, const void* B,
                    const void* Bsc, const void* bias, void* C, int M, int N,
                    int K, bool relu, hipStream_t stream) {
-    if (M % 256 || N % 256 || K % 256 || K < 256) return false;
-    if ((long)M * K >= (1L << 31) || (long)N * K >= (1L << 31)) return false;
-    dim3 grid(M / 256, N / 256);
-    dim3 blk(512);
-    const bool hb = bias != nullptr;
-#define F8LAUNCH(HB, RL)                                                     \
-    hipLaunchKernelGGL((gemm_nt_f8_kernel<HB, RL, false>), grid, blk, 0,     \
-                       stream, (const unsigned char*)A,                      \
-                       (const unsigned char*)Asc, (const unsigned char*)B,   \
-                       (const unsigned char*)Bsc, (const __bf16*)bias,       \
-                       (__bf16*)C, nullptr, nullptr, M, N, K)
-    if (hb && relu) F8LAUNCH(true, true);
-    else if (hb) F8LAUNCH(true, false);
-    else if (relu) F8LAUNCH(false, true);
-    else F8LAUNCH(false, false);
-#undef F8LAUNCH
-    return true;
+    return launch_gemm_f8(A, Asc, B, Bsc, bias, C, nullptr, nullptr, M, N, K,
+                          relu, stream);
 }
 
 // Fused-quant output: C is emitted as (e4m3 data, E8M0 scales) in the
@@ -445,22 +443,6 @@ bool ss_gemm_nt_f8(const void* A, const void* Asc, const void* B,
 bool ss_gemm_nt_f8_q(const void* A, const void* Asc, const void* B,
                      const void* Bsc, const void* bias, void* Cq, void* Cs,
                      int M, int N, int K, bool relu, hipStream_t stream) {
-    if (M % 256 || N % 256 || K % 256 || K < 256) return false;
-    if ((long)M * K >= (1L << 31) || (long)N * K >= (1L << 31)) return false;
-    dim3 grid(M / 256, N / 256);
-    dim3 blk(512);
-    const bool hb = bias != nullptr;
-#define F8QLAUNCH(HB, RL)                                                    \
-    hipLaunchKernelGGL((gemm_nt_f8_kernel<HB, RL, true>), grid, blk, 0,      \
-                       stream, (const unsigned char*)A,                      \
-                       (const unsigned char*)Asc, (const unsigned char*)B,   \
-                       (const unsigned char*)Bsc, (const __bf16*)bias,       \
-                       nullptr, (unsigned char*)Cq, (unsigned char*)Cs, M,   \
-                       N, K)
-    if (hb && relu) F8QLAUNCH(true, true);
-    else if (hb) F8QLAUNCH(true, false);
-    else if (relu) F8QLAUNCH(false, true);
-    else F8QLAUNCH(false, false);
-#undef F8QLAUNCH
-    return true;
+    return launch_gemm_f8(A, Asc, B, Bsc, bias, nullptr, Cq, Cs, M, N, K,
+                          relu, stream);
 }

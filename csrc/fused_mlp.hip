@@ -19,13 +19,16 @@
 // (reference train.py:21-47) as one fused op.
 
 #include "common.h"
+#include "launchers.h"
 
 namespace {
 
 #define FPAD 8  // LDS row padding (ushorts) against bank conflicts
 
 // 64×KSTEP A-chunk (or 256×KSTEP B-chunk) register-staged load, with
-// zero fill beyond (nrows, K) — same structure as gemm.hip's StageReg.
+// zero fill beyond (nrows, K).  Same structure as StageReg<.., false>
+// (stage_reg.h), kept apart: with StageReg this kernel compiles to
+// different instructions (profiles/r06_csrc_common.md).
 template <int TILE_ROWS, int KSTEP, int NT>
 struct FStage {
     static constexpr int EL = TILE_ROWS * KSTEP / NT;

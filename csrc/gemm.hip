@@ -21,103 +21,10 @@
 //     M/N/K (full bounds handling) — launch count, not MFMA peak, is
 //     the budget here.
 
-#include "common.h"
-
-#include <cstdlib>
-
-using bf16x4v = __attribute__((ext_vector_type(4))) __bf16;
-
-#define BK 32
-#define LDS_PAD 8
-// k-group XOR swizzle for transpose-staged tiles (wgrad): spreads the
-// per-instruction m-stride-8 scatter writes over banks (2-way instead
-// of 16-way) while fragment reads stay 16-B-aligned ds_read_b128.
-__device__ __forceinline__ int kswz(int m, int k) {
-    return ((((k) >> 3) ^ (((m) >> 3) & 3)) << 3) | ((k) & 7);
-}
+#include "launchers.h"
+#include "stage_reg.h"
 
 // ---------------------------------------------------------------- gemm_nt
-
-// Staging is split into an ISSUE half (global -> registers, with
-// bounds zero-fill and the optional fused >0 mask) and a WRITE half
-// (registers -> padded LDS tile) so the HBM latency of tile t+1 hides
-// under tile t's MFMA work (async-STAGE split, one barrier per K-step;
-// cdna_hip_programming.md Guideline 15 / T14).
-template <int TILE_ROWS, int KSTEP, int NT, bool HAS_MASK>
-struct StageReg {
-    static constexpr int EL = TILE_ROWS * KSTEP / NT;  // 4..32
-    __bf16 v[EL];
-
-    __device__ __forceinline__ void load(const __bf16* __restrict__ src,
-                                         const __bf16* __restrict__ msk,
-                                         int nrows, int K, int row0, int k0,
-                                         int tid) {
-        const int off = tid * EL;
-        const int r = off / KSTEP, c = off % KSTEP;
-        const int g = row0 + r, gk = k0 + c;
-        if (g < nrows && gk + EL <= K) {
-#pragma unroll
-            for (int ch = 0; ch < EL; ch += (EL < 8 ? 4 : 8)) {
-                if constexpr (EL >= 8) {
-                    bf16x8 t = *(const bf16x8*)&src[(long)g * K + gk + ch];
-                    if constexpr (HAS_MASK) {
-                        bf16x8 mk =
-                            *(const bf16x8*)&msk[(long)g * K + gk + ch];
-#pragma unroll
-                        for (int i = 0; i < 8; ++i)
-                            if (!(bf2f(mk[i]) > 0.f)) t[i] = (__bf16)0.f;
-                    }
-#pragma unroll
-                    for (int i = 0; i < 8; ++i) v[ch + i] = t[i];
-                } else {
-                    bf16x4v t = *(const bf16x4v*)&src[(long)g * K + gk + ch];
-                    if constexpr (HAS_MASK) {
-                        bf16x4v mk =
-                            *(const bf16x4v*)&msk[(long)g * K + gk + ch];
-#pragma unroll
-                        for (int i = 0; i < 4; ++i)
-                            if (!(bf2f(mk[i]) > 0.f)) t[i] = (__bf16)0.f;
-                    }
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) v[ch + i] = t[i];
-                }
-            }
-        } else {
-#pragma unroll
-            for (int i = 0; i < EL; ++i) {
-                __bf16 t = (__bf16)0.f;
-                if (g < nrows && gk + i < K) {
-                    t = src[(long)g * K + gk + i];
-                    if constexpr (HAS_MASK) {
-                        if (!(bf2f(msk[(long)g * K + gk + i]) > 0.f))
-                            t = (__bf16)0.f;
-                    }
-                }
-                v[i] = t;
-            }
-        }
-    }
-
-    __device__ __forceinline__ void write(
-        ushort (*__restrict__ dst)[KSTEP + LDS_PAD], int tid) const {
-        const int off = tid * EL;
-        const int r = off / KSTEP, c = off % KSTEP;
-#pragma unroll
-        for (int ch = 0; ch < EL; ch += (EL < 8 ? 4 : 8)) {
-            if constexpr (EL >= 8) {
-                bf16x8 t;
-#pragma unroll
-                for (int i = 0; i < 8; ++i) t[i] = v[ch + i];
-                *(bf16x8*)&dst[r][c + ch] = t;
-            } else {
-                bf16x4v t;
-#pragma unroll
-                for (int i = 0; i < 4; ++i) t[i] = v[ch + i];
-                *(bf16x4v*)&dst[r][c + ch] = t;
-            }
-        }
-    }
-};
 
 template <int BM, int BN, int KSTEP, int WAVES_M, int WAVES_N,
           bool HAS_BIAS, bool RELU, bool HAS_MASK>
@@ -148,9 +55,7 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64) void gemm_nt_kernel(
     const int gx = gridDim.x, gy = gridDim.y;
     const int nwg = gx * gy;
     const int hw = blockIdx.x + gx * blockIdx.y;
-    const int xcd = hw % 8, q8 = nwg / 8, r8 = nwg % 8;
-    const int wid = (xcd < r8 ? xcd * (q8 + 1)
-                              : r8 * (q8 + 1) + (xcd - r8) * q8) + hw / 8;
+    const int wid = xcd_remap(hw, nwg);
     const int m0 = ((wid / gy) % gx) * BM;
     const int n0 = (wid % gy) * BN;
 
@@ -231,11 +136,6 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64) void gemm_nt_kernel(
     }
 }
 
-// 256-tile 8-phase tier (gemm256.hip) — C++ linkage, declared OUTSIDE
-// the extern "C" launcher block below
-bool ss_gemm_nt_256(const void*, const void*, const void*, void*, int, int,
-                    int, bool, hipStream_t);
-
 // ------------------------------------------------- gemm_nt (glds tier)
 
 // Compute-bound tier (aligned ≥128-multiple shapes, no fused mask):
@@ -254,8 +154,6 @@ __global__ __launch_bounds__(256) void gemm_nt_glds_kernel(
     __bf16* __restrict__ C,           // [M][N]
     int M, int N, int K) {
     constexpr int BM = 128, BN = 128, BKG = 32;
-    typedef __attribute__((address_space(1))) const unsigned int* gptr_t;
-    typedef __attribute__((address_space(3))) unsigned int* lptr_t;
 
     __shared__ ushort As[2][BM * BKG];  // lane-linear [128][32] bf16
     __shared__ ushort Bs[2][BN * BKG];
@@ -270,9 +168,7 @@ __global__ __launch_bounds__(256) void gemm_nt_glds_kernel(
     const int gx = gridDim.x, gy = gridDim.y;
     const int nwg = gx * gy;
     const int hw = blockIdx.x + gx * blockIdx.y;
-    const int xcd = hw % 8, q8 = nwg / 8, r8 = nwg % 8;
-    const int wid = (xcd < r8 ? xcd * (q8 + 1)
-                              : r8 * (q8 + 1) + (xcd - r8) * q8) + hw / 8;
+    const int wid = xcd_remap(hw, nwg);
     const int m0 = ((wid / gy) % gx) * BM;
     const int n0 = (wid % gy) * BN;
 
@@ -447,19 +343,20 @@ __global__ __launch_bounds__(256) void colsum_kernel(
 
 // ---------------------------------------------------------------- launchers
 
-extern "C" {
-
 void ss_gemm_nt(const void* A, const void* B, const void* bias,
                 const void* mask, void* C, int M, int N, int K,
                 bool relu, hipStream_t stream) {
     const bool has_bias = bias != nullptr;
     const bool has_mask = mask != nullptr;
 
-    auto launch = [&](auto bm_tag, auto bias_tag, auto relu_tag, auto mask_tag) {
+    // The register-staged kernel exists in five flavours, not eight:
+    // bias excludes the mask and the mask excludes ReLU (a forward call
+    // has bias/ReLU, a dgrad call has the mask), so the flags are
+    // reduced to those five before they become template arguments.
+    const bool use_mask = has_mask && !has_bias;
+    const bool use_relu = relu && !use_mask;
+    auto launch = [&](auto bm_tag) {
         constexpr int BM = decltype(bm_tag)::value;
-        constexpr bool HB = decltype(bias_tag)::value;
-        constexpr bool RL = decltype(relu_tag)::value;
-        constexpr bool HM = decltype(mask_tag)::value;
         constexpr int BN = BM == 128 ? 128 : 64;
         constexpr int WAVES_M = BM == 32 ? 1 : 2;
         // 4 waves 2x2 everywhere ≥64: 8-wave 128² measured WORSE
@@ -468,48 +365,33 @@ void ss_gemm_nt(const void* A, const void* B, const void* bias,
         constexpr int WAVES_N = BM == 32 ? 4 : 2;
         dim3 block(WAVES_M * WAVES_N * 64);
         dim3 grid(cdiv(M, BM), cdiv(N, BN));
-        // Measured: KSTEP=64 is throughput-neutral at these shapes
-        // (barrier savings offset by the occupancy drop 7->4
-        // blocks/CU), so the deep K-step stays off; the template
-        // keeps it one constant away for wider models.
-        if (false && K >= 512 && BM >= 64) {
-            hipLaunchKernelGGL(
-                (gemm_nt_kernel<BM, BN, 64, WAVES_M, WAVES_N, HB, RL, HM>),
-                grid, block, 0, stream,
-                (const __bf16*)A, (const __bf16*)B, (const __bf16*)bias,
-                (const __bf16*)mask, (__bf16*)C, M, N, K);
-        } else {
-            hipLaunchKernelGGL(
-                (gemm_nt_kernel<BM, BN, 32, WAVES_M, WAVES_N, HB, RL, HM>),
-                grid, block, 0, stream,
-                (const __bf16*)A, (const __bf16*)B, (const __bf16*)bias,
-                (const __bf16*)mask, (__bf16*)C, M, N, K);
-        }
+        with_bools(
+            [&](auto hb, auto rl, auto hm) {
+                // Measured: KSTEP=64 is throughput-neutral at these
+                // shapes (barrier savings offset by the occupancy drop
+                // 7->4 blocks/CU), so every launch uses KSTEP=32; the
+                // template keeps the deep K-step one constant away for
+                // wider models.
+                if constexpr (!(hm.value && (hb.value || rl.value)))
+                    hipLaunchKernelGGL(
+                        (gemm_nt_kernel<BM, BN, 32, WAVES_M, WAVES_N,
+                                        hb.value, rl.value, hm.value>),
+                        grid, block, 0, stream, (const __bf16*)A,
+                        (const __bf16*)B, (const __bf16*)bias,
+                        (const __bf16*)mask, (__bf16*)C, M, N, K);
+            },
+            has_bias, use_relu, use_mask);
     };
-
-    using T = std::true_type;
-    using F = std::false_type;
     using B128 = std::integral_constant<int, 128>;
     using B64 = std::integral_constant<int, 64>;
     using B32 = std::integral_constant<int, 32>;
-
-#define DISPATCH(BMT)                                                  \
-    if (has_bias && relu)        launch(BMT{}, T{}, T{}, F{});         \
-    else if (has_bias)           launch(BMT{}, T{}, F{}, F{});         \
-    else if (has_mask)           launch(BMT{}, F{}, F{}, T{});         \
-    else if (relu)               launch(BMT{}, F{}, T{}, F{});         \
-    else                         launch(BMT{}, F{}, F{}, F{});
 
     // widest tier first: 256-tile 8-phase kernel (gemm256.hip) for
     // aligned wide shapes — measured 1.3-1.6x the 128-glds tier
     // (1027-1293 TF vs 692-811 at 4096-16384 x 4096^2, zero LDS bank
     // conflicts; scripts/test_gemm256.py).  SS_GEMM256=0 disables.
     if (!has_mask && N >= 512 && (long)(M / 256) * (N / 256) >= 128) {
-        static int en256 = -1;
-        if (en256 < 0) {
-            const char* e = getenv("SS_GEMM256");
-            en256 = e ? atoi(e) : 1;
-        }
+        static const int en256 = env_int("SS_GEMM256", 1);
         if (en256 && ss_gemm_nt_256(A, B, bias, C, M, N, K, relu, stream))
             return;
     }
@@ -517,39 +399,29 @@ void ss_gemm_nt(const void* A, const void* B, const void* bias,
     // glds-staged kernel (direct HBM->LDS DMA)
     if (!has_mask && N >= 128 && M % 128 == 0 && N % 128 == 0 &&
         K % 32 == 0 && (long)(M / 128) * (N / 128) >= 512) {
-        dim3 grid(M / 128, N / 128);
-        dim3 blk(256);
-        if (has_bias && relu)
-            hipLaunchKernelGGL((gemm_nt_glds_kernel<true, true>), grid, blk,
-                               0, stream, (const __bf16*)A, (const __bf16*)B,
-                               (const __bf16*)bias, (__bf16*)C, M, N, K);
-        else if (has_bias)
-            hipLaunchKernelGGL((gemm_nt_glds_kernel<true, false>), grid, blk,
-                               0, stream, (const __bf16*)A, (const __bf16*)B,
-                               (const __bf16*)bias, (__bf16*)C, M, N, K);
-        else if (relu)
-            hipLaunchKernelGGL((gemm_nt_glds_kernel<false, true>), grid, blk,
-                               0, stream, (const __bf16*)A, (const __bf16*)B,
-                               (const __bf16*)bias, (__bf16*)C, M, N, K);
-        else
-            hipLaunchKernelGGL((gemm_nt_glds_kernel<false, false>), grid, blk,
-                               0, stream, (const __bf16*)A, (const __bf16*)B,
-                               (const __bf16*)bias, (__bf16*)C, M, N, K);
+        with_bools(
+            [&](auto hb, auto rl) {
+                hipLaunchKernelGGL(
+                    (gemm_nt_glds_kernel<hb.value, rl.value>),
+                    dim3(M / 128, N / 128), dim3(256), 0, stream,
+                    (const __bf16*)A, (const __bf16*)B, (const __bf16*)bias,
+                    (__bf16*)C, M, N, K);
+            },
+            has_bias, relu);
         return;
     }
     // 128x128 only when the grid still covers the CUs with >=2
     // blocks each (1 block/CU = 4 waves starves latency hiding)
     if (N >= 128 && (long)cdiv(M, 128) * cdiv(N, 128) >= 512) {
-        DISPATCH(B128)
+        launch(B128{});
     } else if (M < 48 ||
                (long)cdiv(M, 64) * cdiv(N, 64) < 192) {
         // small-M / small-grid shapes: the 32-row config doubles the
         // block count (latency-bound regime — µbatched schedules)
-        DISPATCH(B32)
+        launch(B32{});
     } else {
-        DISPATCH(B64)
+        launch(B64{});
     }
-#undef DISPATCH
 }
 
 void ss_colsum(const void* dY, const void* mask, void* gb, int M, int N,
@@ -564,27 +436,18 @@ void ss_colsum(const void* dY, const void* mask, void* gb, int M, int N,
     int rows_per_block = cdiv(M, splits);
     dim3 grid(col_tiles, splits);
     dim3 block(256);
-    if (vec8) {
-        if (mask)
-            hipLaunchKernelGGL((colsum8_kernel<true>), grid, block, 0,
-                               stream, (const __bf16*)dY,
-                               (const __bf16*)mask, (float*)gb, M, N,
-                               rows_per_block);
-        else
-            hipLaunchKernelGGL((colsum8_kernel<false>), grid, block, 0,
-                               stream, (const __bf16*)dY,
-                               (const __bf16*)mask, (float*)gb, M, N,
-                               rows_per_block);
-        return;
-    }
-    if (mask)
-        hipLaunchKernelGGL((colsum_kernel<true>), grid, block, 0, stream,
-                           (const __bf16*)dY, (const __bf16*)mask, (float*)gb,
-                           M, N, rows_per_block);
-    else
-        hipLaunchKernelGGL((colsum_kernel<false>), grid, block, 0, stream,
-                           (const __bf16*)dY, (const __bf16*)mask, (float*)gb,
-                           M, N, rows_per_block);
+    with_bools(
+        [&](auto v8, auto hm) {
+            if constexpr (v8.value)
+                hipLaunchKernelGGL((colsum8_kernel<hm.value>), grid, block, 0,
+                                   stream, (const __bf16*)dY,
+                                   (const __bf16*)mask, (float*)gb, M, N,
+                                   rows_per_block);
+            else
+                hipLaunchKernelGGL((colsum_kernel<hm.value>), grid, block, 0,
+                                   stream, (const __bf16*)dY,
+                                   (const __bf16*)mask, (float*)gb, M, N,
+                                   rows_per_block);
+        },
+        vec8, mask != nullptr);
 }
-
-}  // extern "C"

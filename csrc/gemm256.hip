@@ -39,15 +39,9 @@
 // functional.py:13-21 of the reference, at wide-model shapes.
 
 #include "common.h"
+#include "launchers.h"
 
 namespace {
-
-typedef __attribute__((address_space(1))) const unsigned int* gptr_t;
-typedef __attribute__((address_space(3))) unsigned int* lptr_t;
-
-#define SS_VMCNT(n) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(n))
-#define SS_LGKM(n) asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(n))
-#define SS_BAR() __builtin_amdgcn_s_barrier()
 
 template <bool HAS_BIAS, bool RELU>
 __global__ __launch_bounds__(512, 1) void gemm_nt_256_kernel(
@@ -71,9 +65,7 @@ __global__ __launch_bounds__(512, 1) void gemm_nt_256_kernel(
     const int gx = gridDim.x, gy = gridDim.y;
     const int nwg = gx * gy;
     const int hw = blockIdx.x + gx * blockIdx.y;
-    const int xcd = hw % 8, q8 = nwg / 8, r8 = nwg % 8;
-    const int wid = (xcd < r8 ? xcd * (q8 + 1)
-                              : r8 * (q8 + 1) + (xcd - r8) * q8) + hw / 8;
+    const int wid = xcd_remap(hw, nwg);
     const int m0 = ((wid / gy) % gx) * 256;
     const int n0 = (wid % gy) * 256;
 
@@ -278,24 +270,13 @@ bool ss_gemm_nt_256(const void* A, const void* B, const void* bias, void* C,
     // 32-bit per-lane source offsets in the kernel
     if ((long)M * K * 2 >= (1L << 31) || (long)N * K * 2 >= (1L << 31))
         return false;
-    const bool has_bias = bias != nullptr;
-    dim3 grid(M / 256, N / 256);
-    dim3 blk(512);
-    if (has_bias && relu)
-        hipLaunchKernelGGL((gemm_nt_256_kernel<true, true>), grid, blk, 0,
-                           stream, (const __bf16*)A, (const __bf16*)B,
-                           (const __bf16*)bias, (__bf16*)C, M, N, K);
-    else if (has_bias)
-        hipLaunchKernelGGL((gemm_nt_256_kernel<true, false>), grid, blk, 0,
-                           stream, (const __bf16*)A, (const __bf16*)B,
-                           (const __bf16*)bias, (__bf16*)C, M, N, K);
-    else if (relu)
-        hipLaunchKernelGGL((gemm_nt_256_kernel<false, true>), grid, blk, 0,
-                           stream, (const __bf16*)A, (const __bf16*)B,
-                           nullptr, (__bf16*)C, M, N, K);
-    else
-        hipLaunchKernelGGL((gemm_nt_256_kernel<false, false>), grid, blk, 0,
-                           stream, (const __bf16*)A, (const __bf16*)B,
-                           nullptr, (__bf16*)C, M, N, K);
+    with_bools(
+        [&](auto hb, auto rl) {
+            hipLaunchKernelGGL((gemm_nt_256_kernel<hb.value, rl.value>),
+                               dim3(M / 256, N / 256), dim3(512), 0, stream,
+                               (const __bf16*)A, (const __bf16*)B,
+                               (const __bf16*)bias, (__bf16*)C, M, N, K);
+        },
+        bias != nullptr, relu);
     return true;
 }

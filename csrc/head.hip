@@ -36,10 +36,10 @@
 // nonfinite only.
 
 #include "common.h"
+#include "launchers.h"
 
 #include <climits>
 #include <cmath>
-#include <cstdlib>
 
 namespace {
 
@@ -599,10 +599,7 @@ bool ss_head_bwd_fused(const void* probs, const void* target, const void* x,
     // without gW the grid is not capped: 32-row tiles put two blocks on
     // a CU, whose load / MFMA / store phases then overlap
     // SS_HEAD_BWD_ROWS (read once) overrides the choice for tuning.
-    static const int env_rows = [] {
-        const char* e = getenv("SS_HEAD_BWD_ROWS");
-        return e ? atoi(e) : 0;
-    }();
+    static const int env_rows = env_int("SS_HEAD_BWD_ROWS", 0);
     if (!rows_per_block) rows_per_block = env_rows;
     const int rb = rows_per_block ? rows_per_block : (gW ? 64 : 32);
     // the 128-row arm halves the column chunk to stay inside 64 KB of LDS

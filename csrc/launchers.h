@@ -1,0 +1,103 @@
+// Host launchers of the HIP kernels: the one declaration of each.
+//
+// Every .hip file that defines a launcher includes this header, and so
+// does bindings.cpp.  All have C++ linkage, so a parameter list that
+// changes on one side only is another overload: the call or the symbol
+// then has no match and the build fails, at the latest when it imports
+// the extension, instead of passing arguments in the wrong slots.
+// Pointers are untyped device
+// pointers; every launcher enqueues on `stream` and returns at once.
+// The bool launchers return false, with nothing launched, when the
+// shape is outside their kernel's contract.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+// ---- gemm.hip
+void ss_gemm_nt(const void* A, const void* B, const void* bias,
+                const void* mask, void* C, int M, int N, int K, bool relu,
+                hipStream_t stream);
+void ss_colsum(const void* dY, const void* mask, void* gb, int M, int N,
+               hipStream_t stream);
+
+// ---- gemm256.hip / gemm256w.hip
+bool ss_gemm_nt_256(const void* A, const void* B, const void* bias, void* C,
+                    int M, int N, int K, bool relu, hipStream_t stream);
+bool ss_gemm_nt_256w(const void* A, const void* B, const void* bias, void* C,
+                     int M, int N, int K, bool relu, hipStream_t stream);
+
+// ---- fp8.hip
+void ss_fp8_quantize(const void* X, void* Q, void* S, int R, int K,
+                     hipStream_t stream);
+bool ss_gemm_nt_f8(const void* A, const void* Asc, const void* B,
+                   const void* Bsc, const void* bias, void* C, int M, int N,
+                   int K, bool relu, hipStream_t stream);
+bool ss_gemm_nt_f8_q(const void* A, const void* Asc, const void* B,
+                     const void* Bsc, const void* bias, void* Cq, void* Cs,
+                     int M, int N, int K, bool relu, hipStream_t stream);
+
+// ---- wgrad.hip / wgrad256.hip
+void ss_wgrad_tn(const void* dY, const void* X, const void* mask, void* gW,
+                 void* gb, int Mo, int N, int Kb, int split_k,
+                 hipStream_t stream);
+void ss_wgrad_tn_multi(const void* chunk_table, int nchunks, bool has_mask,
+                       void* gW, void* gb, int Mo, int N, int Kb_chunk,
+                       int split_k, hipStream_t stream);
+bool ss_wgrad_tn_256(const void* dY, const void* X, void* gW, int Mo, int N,
+                     int Kb, hipStream_t stream);
+
+// ---- head.hip
+bool ss_head_fwd_fused(const void* x, const void* W, const void* bias,
+                       void* probs, int M, int K, int C, int rows_per_block,
+                       hipStream_t stream);
+bool ss_head_bwd_fused(const void* probs, const void* target, const void* x,
+                       const void* Wt, void* dz, void* dx, void* gW, void* gb,
+                       int M, int K, int C, float inv_gb, int rows_per_block,
+                       void* metrics, int slots, hipStream_t stream);
+bool ss_head_metrics(const void* probs, const void* target, void* acc,
+                     int slots, int M, int C, int kind, hipStream_t stream);
+
+// ---- fused_mlp.hip
+bool ss_fused_mlp_fwd(const void* x, const void* desc, int M, int in_dim,
+                      int nhidden, int cout, void* out, hipStream_t stream);
+
+// ---- elementwise.hip
+void ss_relu_fwd(const void* x, void* y, long n, hipStream_t stream);
+void ss_relu_bwd(const void* dy, const void* y, void* dx, long n,
+                 hipStream_t stream);
+void ss_softmax_fwd(const void* x, void* s, int B, int C, hipStream_t stream);
+void ss_softmax_bwd(const void* dy, const void* s, void* dx, int B, int C,
+                    hipStream_t stream);
+void ss_head_mse_bwd(const void* s, const void* t, void* dz, int B, int C,
+                     float inv_gb, hipStream_t stream);
+void ss_head_xent_bwd(const void* s, const void* t, void* dz, long n,
+                      float inv_gb, hipStream_t stream);
+void ss_row_argmax(const void* x, void* out, int B, int C,
+                   hipStream_t stream);
+void ss_transpose_bf16(const void* src, void* dst, int rows, int cols,
+                       hipStream_t stream);
+void ss_sgd_multi(const void* desc, int ntensors, long total, float lr,
+                  float momentum, float weight_decay, hipStream_t stream);
+void ss_adamw_multi(const void* desc, int ntensors, long total, float lr,
+                    float beta1, float beta2, float eps, float weight_decay,
+                    float inv_bc1, float inv_bc2, hipStream_t stream);
+void ss_sgd_multi2(const void* desc, const void* bmap, int nblocks, float lr,
+                   float momentum, float weight_decay, hipStream_t stream);
+void ss_adamw_multi2(const void* desc, const void* bmap, int nblocks,
+                     float lr, float beta1, float beta2, float eps,
+                     float weight_decay, float inv_bc1, float inv_bc2,
+                     hipStream_t stream);
+
+// ---- norm.hip
+void ss_ln_fwd(const void* x, const void* gamma, const void* beta, void* y,
+               void* mean, void* rstd, int B, int C, float eps,
+               hipStream_t stream);
+void ss_ln_bwd_dx(const void* dy, const void* x, const void* gamma,
+                  const void* mean, const void* rstd, void* dx, int B, int C,
+                  hipStream_t stream);
+void ss_ln_bwd_dparam(const void* dy, const void* x, const void* mean,
+                      const void* rstd, void* dgamma, void* dbeta, int B,
+                      int C, hipStream_t stream);
+void ss_gelu_fwd(const void* z, void* y, long n, hipStream_t stream);
+void ss_gelu_bwd(const void* dy, const void* z, void* dz, long n,
+                 hipStream_t stream);

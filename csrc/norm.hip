@@ -11,12 +11,7 @@
 //   bwd needs the PRE-activation z (stashed by the layer).
 
 #include "common.h"
-
-__device__ __forceinline__ float wsum(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
+#include "launchers.h"
 
 // --------------------------------------------------------------- layernorm
 
@@ -35,8 +30,8 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(
         s += v;
         s2 += v * v;
     }
-    s = wsum(s);
-    s2 = wsum(s2);
+    s = wave_sum(s);
+    s2 = wave_sum(s2);
     const float mu = s / C;
     const float var = s2 / C - mu * mu;
     const float rs = rsqrtf(var + eps);
@@ -68,8 +63,8 @@ __global__ __launch_bounds__(256) void ln_bwd_dx_kernel(
         sg += g;
         sgx += g * xh;
     }
-    sg = wsum(sg) / C;
-    sgx = wsum(sgx) / C;
+    sg = wave_sum(sg) / C;
+    sgx = wave_sum(sgx) / C;
     __bf16* dxr = dx + (long)row * C;
     for (int c = lane; c < C; c += 64) {
         const float g = bf2f(dyr[c]) * bf2f(gamma[c]);
@@ -150,15 +145,6 @@ __global__ __launch_bounds__(256) void gelu_bwd_kernel(
 
 // ---------------------------------------------------------------- launchers
 
-extern "C" {
-
-static inline int ngrid(long n) {
-    long b = (n / 8 + 255) / 256;
-    if (b < 1) b = 1;
-    if (b > 2048) b = 2048;
-    return (int)b;
-}
-
 void ss_ln_fwd(const void* x, const void* gamma, const void* beta, void* y,
                void* mean, void* rstd, int B, int C, float eps,
                hipStream_t st) {
@@ -192,14 +178,12 @@ void ss_ln_bwd_dparam(const void* dy, const void* x, const void* mean,
 }
 
 void ss_gelu_fwd(const void* z, void* y, long n, hipStream_t st) {
-    hipLaunchKernelGGL(gelu_fwd_kernel, dim3(ngrid(n)), dim3(256), 0, st,
+    hipLaunchKernelGGL(gelu_fwd_kernel, dim3(ew_grid(n)), dim3(256), 0, st,
                        (const __bf16*)z, (__bf16*)y, n);
 }
 
 void ss_gelu_bwd(const void* dy, const void* z, void* dz, long n,
                  hipStream_t st) {
-    hipLaunchKernelGGL(gelu_bwd_kernel, dim3(ngrid(n)), dim3(256), 0, st,
+    hipLaunchKernelGGL(gelu_bwd_kernel, dim3(ew_grid(n)), dim3(256), 0, st,
                        (const __bf16*)dy, (const __bf16*)z, (__bf16*)dz, n);
 }
-
-}  // extern "C"

@@ -20,19 +20,11 @@
 // the full-rate shape).  There is no inter-block protocol.
 
 #include "common.h"
+#include "launchers.h"
 
-#include <cstdlib>
-
-using bf16x4v = __attribute__((ext_vector_type(4))) __bf16;
 // operands in the global address space (see the kernel's pointer note)
 using gbf16 = __attribute__((address_space(1))) __bf16;
 using gbf16x8 = __attribute__((address_space(1))) bf16x8;
-
-// 256-tile 8-phase tier (wgrad256.hip) — C++ linkage
-bool ss_wgrad_tn_256(const void*, const void*, void*, int, int, int,
-                     hipStream_t);
-extern "C" void ss_colsum(const void*, const void*, void*, int, int,
-                          hipStream_t);
 
 // Second launch bound = waves per SIMD the register allocation must
 // leave room for: accumulators + the prefetch set + fragments stay
@@ -104,9 +96,7 @@ void wgrad_tn_kernel(
     const int gx = gridDim.x, gy = gridDim.y;
     const int nwg = gx * gy * gridDim.z;
     const int hw = blockIdx.x + gx * (blockIdx.y + gy * blockIdx.z);
-    const int xcd = hw % 8, q = nwg / 8, r = nwg % 8;
-    const int wid = (xcd < r ? xcd * (q + 1)
-                             : r * (q + 1) + (xcd - r) * q) + hw / 8;
+    const int wid = xcd_remap(hw, nwg);
     const int bidy = wid % gy;
     const int bidx = (wid / gy) % gx;
     int bidz = wid / (gy * gx);
@@ -286,8 +276,6 @@ void wgrad_tn_kernel(
     // lane-linear; piece q -> position p = q/8 (mblk = p/16, ksub =
     // swsub(p&15)), r = q%8 -> global (k = ksub*4 + (r>>1), m =
     // mblk*16 + (r&1)*8).  The four waves of a group fill its image.
-    typedef __attribute__((address_space(1))) const unsigned int* ggptr_t;
-    typedef __attribute__((address_space(3))) unsigned int* glptr_t;
     auto glds_stage = [&](const gbf16* src, ushort* img,
                           int nmt, int ld, int base_col, int gk0) {
         const int total = nmt * 16 * 8;          // pieces
@@ -300,8 +288,8 @@ void wgrad_tn_kernel(
             const int k = ksub * 4 + (rr >> 1);
             const int m = (p >> 4) * 16 + (rr & 1) * 8;
             __builtin_amdgcn_global_load_lds(
-                (ggptr_t)(src + (long)(gk0 + k) * ld + base_col + m),
-                (glptr_t)(img + (long)(wave * per_wave + i0) * 8), 16, 0,
+                (gptr_t)(src + (long)(gk0 + k) * ld + base_col + m),
+                (lptr_t)(img + (long)(wave * per_wave + i0) * 8), 16, 0,
                 0);
         }
     };
@@ -311,7 +299,6 @@ void wgrad_tn_kernel(
     };
 
     // ---- fragments via hardware transpose read, then MFMA ----
-    typedef __attribute__((address_space(3))) bf16x4v* lds_v4p;
     const int lcol4 = (lane & 15) * 4;
     auto mma_step = [&](auto all_cols) {
         // all_cols false: only the first 16-column fragment (a wave
@@ -485,11 +472,6 @@ constexpr int WGRAD_KG_64 = 4;   // 64x64 tiles
 // blocks the auto split aims for: one per CU
 constexpr int WGRAD_TARGET_BLOCKS = 256;
 
-int env_int(const char* name, int dflt) {
-    const char* e = getenv(name);
-    return e ? atoi(e) : dflt;
-}
-
 // tile and K-group choice shared by the plain and the chunked launcher
 struct WgradCfg {
     int bm, bn, kg;
@@ -562,8 +544,6 @@ int wgrad_auto_split(int tiles, int Kb, int kg) {
         }                                                                   \
     } while (0)
 
-extern "C" {
-
 void ss_wgrad_tn(const void* dY, const void* X, const void* mask, void* gW,
                  void* gb, int Mo, int N, int Kb, int split_k,
                  hipStream_t stream) {
@@ -607,5 +587,3 @@ void ss_wgrad_tn_multi(const void* chunk_table, int nchunks, bool has_mask,
                    (const __bf16*)nullptr, (float*)gW, (float*)gb, Mo, N,
                    Kb_chunk, k_per_split, (const long*)chunk_table, split_k);
 }
-
-}  // extern "C"

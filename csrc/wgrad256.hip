@@ -31,16 +31,9 @@
 // scripts/test_gemm256.py --wgrad / profiles/r01_kernel_stats.md.
 
 #include "common.h"
+#include "launchers.h"
 
 namespace {
-
-typedef __attribute__((address_space(1))) const unsigned int* gptr_t;
-typedef __attribute__((address_space(3))) unsigned int* lptr_t;
-
-using bf16x4v = __attribute__((ext_vector_type(4))) __bf16;
-typedef __attribute__((address_space(3))) bf16x4v* lds_v4p;
-
-#define SS_VMCNT(n) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(n))
 
 // Raw-asm transpose read: the ds_read_tr INTRINSIC's LDS-read memory
 // effect makes SIInsertWaitcnts order it against in-flight LDS-DMA
@@ -51,8 +44,6 @@ __device__ __forceinline__ bf16x4v tr_read(lds_v4p p) {
     asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(out) : "v"(p));
     return out;
 }
-#define SS_LGKM(n) asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(n))
-#define SS_BAR() __builtin_amdgcn_s_barrier()
 
 __device__ __forceinline__ int swap01(int x) {
     return (x & ~3) | ((x & 1) << 1) | ((x >> 1) & 1);
@@ -76,9 +67,7 @@ __global__ __launch_bounds__(512, 1) void wgrad_tn_256_kernel(
     const int gx = gridDim.x, gy = gridDim.y;
     const int nwg = gx * gy * gridDim.z;
     const int hw = blockIdx.x + gx * (blockIdx.y + gy * blockIdx.z);
-    const int xcd = hw % 8, q8 = nwg / 8, r8 = nwg % 8;
-    const int wid = (xcd < r8 ? xcd * (q8 + 1)
-                              : r8 * (q8 + 1) + (xcd - r8) * q8) + hw / 8;
+    const int wid = xcd_remap(hw, nwg);
     const int m0 = ((wid / gy) % gx) * 256;
     const int n0 = (wid % gy) * 256;
     const int kbeg = (wid / (gx * gy)) * k_per_split;

@@ -739,3 +739,122 @@ def test_fused_mlp_fwd_matches_eager(gpu_device):
                 sizes, mm[:5].tolist())
         assert mm.numel() <= max(1, probs.shape[0] // 50), (
             sizes, mm.numel())  # ties must stay rare
+
+
+# ------------------------------------- launch ladders, one case per rung
+
+FLAG_COMBOS = [(False, False), (True, False), (False, True), (True, True)]
+
+
+def _mx_dequant(q, s):
+    """e4m3 bytes [R,K] + e8m0 scales [K/128,R,4] -> f32 (the oracle of
+    test_fp8_quantize_and_gemm)."""
+    K = q.shape[1]
+    qf = q.to(torch.int32)
+    sgn = torch.where(qf >= 128, -1.0, 1.0)
+    qa = qf & 0x7F
+    ee = qa >> 3
+    m = (qa & 7).float()
+    mag = torch.where(ee == 0, (m / 8.0) * 2.0 ** -6,
+                      (1 + m / 8.0) * torch.pow(2.0, ee.float() - 7))
+    k = torch.arange(K, device=q.device)
+    g = ((k >> 6) & 1) + 2 * ((k >> 4) & 1)
+    sc = s.to(torch.int32)[k >> 7, :, g].t().float()
+    return sgn * mag * torch.pow(2.0, sc - 127)
+
+
+def _epilogue(ref, bias, bias_on, relu):
+    if bias_on:
+        ref = ref + bias.float()
+    return torch.clamp(ref, min=0) if relu else ref
+
+
+@pytest.mark.parametrize("shape", [
+    (32, 64, 32), (1024, 768, 32), (8200, 1024, 32), (8192, 1024, 32),
+], ids=["rows32", "rows64", "reg128", "glds"])
+def test_gemm_nt_epilogue_ladder(gpu_device, shape):
+    """Every (bias, relu) combination plus mask-alone through each
+    gemm_nt tier, so a ladder with swapped or dropped flags fails.  The
+    gates of ss_gemm_nt send the shapes to their tiers:
+      32x64x32      M < 48 -> 32-row configuration
+      1024x768x32   16x12 = 192 blocks of 64^2 (not < 192) and 8x6 = 48
+                    blocks of 128^2 (< 512) -> 64-row configuration
+      8200x1024x32  65x8 = 520 blocks of 128^2 (>= 512); M % 128 != 0
+                    keeps it off the glds tier, M % 256 != 0 makes the
+                    256 tier decline -> 128^2 register-staged kernel
+      8192x1024x32  64x8 = 512 aligned blocks of 128^2; K % 128 != 0
+                    makes the 256 tier decline -> gemm_nt_glds_kernel
+    A mask keeps every shape off the 256 and glds tiers, so mask-alone
+    at the last shape runs the masked 128^2 register-staged kernel."""
+    M, N, K = shape
+    e = ext()
+    a = rand_bf16(M, K, device=gpu_device, seed=100)
+    b = rand_bf16(N, K, device=gpu_device, seed=101)
+    bias = rand_bf16(N, device=gpu_device, seed=102)
+    mask = rand_bf16(M, K, device=gpu_device, seed=103)
+    empty = torch.Tensor()
+    base = a.float() @ b.float().t()
+    for bias_on, relu in FLAG_COMBOS:
+        c = e.gemm_nt(a, b, bias if bias_on else empty, empty, relu)
+        ref = _epilogue(base, bias, bias_on, relu)
+        torch.testing.assert_close(c.float(), ref, **tol(ref),
+                                   msg=lambda m: f"{bias_on=} {relu=}: {m}")
+    c = e.gemm_nt(a, b, empty, mask, False)
+    ref = (a.float() * (mask.float() > 0)) @ b.float().t()
+    torch.testing.assert_close(c.float(), ref, **tol(ref))
+
+
+def test_gemm_nt_f8_epilogue_ladder(gpu_device):
+    """All four (bias, relu) combinations of gemm_nt_f8 against the
+    dequantised-operand oracle, and of gemm_nt_f8_q against the
+    bf16-output call (within one e4m3 ulp, as
+    test_fp8_fused_quant_output), at 256x256x256 (one 256-tile)."""
+    e = ext()
+    M = N = K = 256
+    a = rand_bf16(M, K, device=gpu_device, seed=110)
+    b = rand_bf16(N, K, device=gpu_device, seed=111)
+    bias = rand_bf16(N, device=gpu_device, seed=112)
+    qa, sa = e.fp8_quantize(a)
+    qb, sb = e.fp8_quantize(b)
+    base = _mx_dequant(qa, sa) @ _mx_dequant(qb, sb).t()
+    for bias_on, relu in FLAG_COMBOS:
+        bt = bias if bias_on else torch.Tensor()
+        c16 = e.gemm_nt_f8(qa, sa, qb, sb, bt, relu).float()
+        want = _epilogue(base, bias, bias_on, relu)
+        torch.testing.assert_close(c16, want, **tol(want, atol=0.05),
+                                   msg=lambda m: f"{bias_on=} {relu=}: {m}")
+        cq, cs = e.gemm_nt_f8_q(qa, sa, qb, sb, bt, relu)
+        cd = _mx_dequant(cq, cs)
+        rel = ((cd - c16).abs() / c16.abs().clamp_min(4.0)).max().item()
+        assert rel < 0.07, (bias_on, relu, rel)
+
+
+@pytest.mark.parametrize("bias_on,relu", FLAG_COMBOS)
+def test_gemm_nt_256w_epilogue_ladder(gpu_device, bias_on, relu):
+    """The 4-wave 256-tile variant (gemm256w.hip) with each (bias, relu)
+    combination at 256x256x128 (one tile, one K-step pair) vs f32 torch."""
+    e = ext()
+    M, N, K = 256, 256, 128
+    a = rand_bf16(M, K, device=gpu_device, seed=120)
+    b = rand_bf16(N, K, device=gpu_device, seed=121)
+    bias = rand_bf16(N, device=gpu_device, seed=122)
+    c = e.gemm_nt_256w(a, b, bias if bias_on else torch.Tensor(), relu)
+    ref = _epilogue(a.float() @ b.float().t(), bias, bias_on, relu)
+    torch.testing.assert_close(c.float(), ref, **tol(ref, atol=0.05))
+
+
+@pytest.mark.parametrize("N", [2048, 40])
+@pytest.mark.parametrize("masked", [False, True])
+def test_colsum_mask_ladder(gpu_device, N, masked):
+    """Standalone colsum with and without mask: N = 2048 takes the
+    8-wide kernel (N % 8 == 0 and N >= 2048), N = 40 the scalar one."""
+    e = ext()
+    M = 64
+    dy = rand_bf16(M, N, device=gpu_device, seed=130)
+    mask = rand_bf16(M, N, device=gpu_device, seed=131)
+    gb = e.colsum(dy, mask if masked else torch.Tensor())
+    ref = dy.float()
+    if masked:
+        ref = ref * (mask.float() > 0)
+    ref = ref.sum(0)
+    torch.testing.assert_close(gb, ref, **tol(ref))
