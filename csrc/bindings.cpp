@@ -370,6 +370,67 @@ std::vector<torch::Tensor> head_bwd_fused(torch::Tensor probs,
     return {dz, dx};
 }
 
+// Backward chain (bwd_chain.hip): head backward and the 256-wide ReLU
+// layers' data gradients below it in one launch.  hs[l] / w_ts[l], top
+// layer first: the layer's post-ReLU output and its W^T; w_ts holds one
+// entry per dgrad in the chain, so len(w_ts) is len(hs) (dx of the last
+// layer is returned too) or len(hs) - 1 (the chain ends at dz of the
+// last layer).  Returns [dz_head, dz_0, ..., dz_{n-1}(, dx)], or an
+// EMPTY list, with nothing launched, when the inputs are outside the
+// kernel's contract: the caller then takes the per-layer path.
+std::vector<torch::Tensor> bwd_chain(torch::Tensor probs, torch::Tensor target,
+                                     torch::Tensor w_head_t,
+                                     double global_batch,
+                                     std::vector<torch::Tensor> hs,
+                                     std::vector<torch::Tensor> w_ts,
+                                     int64_t rows, int64_t waves,
+                                     int64_t w_lds) {
+    auto plain = [](const torch::Tensor& t) {
+        return t.is_cuda() && t.scalar_type() == torch::kBFloat16 &&
+               t.dim() == 2 && t.is_contiguous() &&
+               ((uintptr_t)t.data_ptr() & 15) == 0;
+    };
+    const int64_t n = (int64_t)hs.size();
+    const int64_t nw = (int64_t)w_ts.size();
+    if (n < 1 || n > SS_BWD_CHAIN_MAX || (nw != n && nw != n - 1)) return {};
+    if (!plain(probs) || !plain(target) || !plain(w_head_t)) return {};
+    if (probs.sizes() != target.sizes()) return {};
+    const int64_t M = probs.size(0), C = probs.size(1), H = w_head_t.size(0);
+    if (M < 1 || M > INT_MAX / 512 || w_head_t.size(1) != C) return {};
+    const void* hp[SS_BWD_CHAIN_MAX] = {};
+    const void* wp[SS_BWD_CHAIN_MAX] = {};
+    void* dp[SS_BWD_CHAIN_MAX] = {};
+    for (int64_t l = 0; l < n; ++l) {
+        if (!plain(hs[l]) || hs[l].size(0) != M || hs[l].size(1) != H)
+            return {};
+        hp[l] = hs[l].data_ptr();
+        if (l < nw) {
+            if (!plain(w_ts[l]) || w_ts[l].size(0) != H ||
+                w_ts[l].size(1) != H)
+                return {};
+            wp[l] = w_ts[l].data_ptr();
+        }
+    }
+    std::vector<torch::Tensor> out;
+    out.push_back(torch::empty_like(probs));
+    for (int64_t l = 0; l < n; ++l) {
+        out.push_back(torch::empty_like(hs[l]));
+        dp[l] = out.back().data_ptr();
+    }
+    void* dx_p = nullptr;
+    if (nw == n) {
+        out.push_back(torch::empty_like(hs[n - 1]));
+        dx_p = out.back().data_ptr();
+    }
+    if (!ss_bwd_chain(probs.data_ptr(), target.data_ptr(),
+                      w_head_t.data_ptr(), out[0].data_ptr(), hp, wp, dp,
+                      (int)n, dx_p, (int)M, (int)H, (int)C,
+                      (float)(1.0 / global_batch), (int)rows, (int)waves,
+                      (int)w_lds, cur_stream()))
+        return {};
+    return out;
+}
+
 // Adds the metric totals of (probs, target) into acc: loss_sum (kind
 // "xent" or "mse"), argmax matches, rows, non-finite rows.
 void head_metrics(torch::Tensor probs, torch::Tensor target,
@@ -562,6 +623,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           py::arg("global_batch"), py::arg("grad_w"), py::arg("grad_b"),
           py::arg("rows_per_block") = 0,
           py::arg("metrics") = py::none(), py::arg("slots") = 0);
+    m.def("bwd_chain", &bwd_chain,
+          "head backward + 256-wide ReLU dgrads in one launch -> "
+          "[dz_head, dz_l..., (dx)], or [] outside the contract",
+          py::arg("probs"), py::arg("target"), py::arg("w_head_t"),
+          py::arg("global_batch"), py::arg("hs"), py::arg("w_ts"),
+          py::arg("rows") = 0, py::arg("waves") = 0, py::arg("w_lds") = 0);
     m.def("head_metrics", &head_metrics,
           "metric totals of (probs, target) into a slotted accumulator",
           py::arg("probs"), py::arg("target"), py::arg("acc"),

@@ -35,24 +35,13 @@
 // folds the slots.  A row with a NaN or Inf prob counts in rows and
 // nonfinite only.
 
-#include "common.h"
+#include "head_dev.h"
 #include "launchers.h"
 
 #include <climits>
 #include <cmath>
 
 namespace {
-
-__device__ __forceinline__ bf16x8 zero8() {
-    bf16x8 z;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) z[i] = (__bf16)0.f;
-    return z;
-}
-
-__device__ __forceinline__ ushort bf_bits(__bf16 v) {
-    return *(const ushort*)&v;
-}
 
 constexpr float SS_FLT_MIN = 1.17549435e-38f;
 
@@ -286,22 +275,7 @@ __global__ __launch_bounds__(256) void head_bwd_fused_kernel(
         const bool first = k0 == 0;
 
         // W^T rows of this chunk, zero-padded to 16 classes
-        if (tid < KC) {
-            __bf16 w[16];
-#pragma unroll
-            for (int c = 0; c < 16; ++c) {
-                w[c] = (__bf16)0.f;
-                if (tid < kc && c < C) w[c] = Wt[(long)(k0 + tid) * C + c];
-            }
-            bf16x8 lo, hi;
-#pragma unroll
-            for (int c = 0; c < 8; ++c) {
-                lo[c] = w[c];
-                hi[c] = w[c + 8];
-            }
-            *(bf16x8*)&wts[tid][0] = lo;
-            *(bf16x8*)&wts[tid][8] = hi;
-        }
+        HEAD_STAGE_WT(KC, wts, Wt, k0, kc, C, tid)
 
         float gw[C4 * 4];
 #pragma unroll
@@ -336,7 +310,7 @@ __global__ __launch_bounds__(256) void head_bwd_fused_kernel(
                 if (c < C && row0 + r < M) {
                     const long gi = (long)(row0 + r) * C + c;
                     const __bf16 pb = probs[gi], tb = target[gi];
-                    const __bf16 o = f2bf((bf2f(pb) - bf2f(tb)) * inv_gb);
+                    const __bf16 o = head_dz_elem(pb, tb, inv_gb);
                     if (first) dz[gi] = o;
                     d = bf2f(o);
                     bits = bf_bits(o);
@@ -379,14 +353,7 @@ __global__ __launch_bounds__(256) void head_bwd_fused_kernel(
             const int nfrag = NRG * (kc / 16);
             for (int idx = wave; idx < nfrag; idx += 4) {
                 const int rg = idx % NRG, ct = idx / NRG;
-                bf16x8 af = zero8(), bfr = zero8();
-                if (kch < 2) {
-                    af = *(const bf16x8*)&dzs[rg * 16 + lrow][kch * 8];
-                    bfr = *(const bf16x8*)&wts[ct * 16 + lrow][kch * 8];
-                }
-                f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-                acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af, bfr, acc, 0,
-                                                              0, 0);
+                HEAD_DX_FRAG(acc, dzs, wts, rg, ct, lrow, kch);
 #pragma unroll
                 for (int r = 0; r < 4; ++r)
                     tile[rg * 16 + kch * 4 + r][ct * 16 + lrow] =

@@ -57,6 +57,16 @@ bool ss_head_bwd_fused(const void* probs, const void* target, const void* x,
 bool ss_head_metrics(const void* probs, const void* target, void* acc,
                      int slots, int M, int C, int kind, hipStream_t stream);
 
+// ---- bwd_chain.hip
+// h / wt / dz: nlayers pointers each, top layer first (post-ReLU output,
+// W^T or null where the chain ends, masked gradient out).
+constexpr int SS_BWD_CHAIN_MAX = 8;
+bool ss_bwd_chain(const void* probs, const void* target, const void* Wt_head,
+                  void* dz_head, const void* const* h, const void* const* wt,
+                  void* const* dz, int nlayers, void* dx, int M, int H, int C,
+                  float inv_gb, int rows, int waves, int w_lds,
+                  hipStream_t stream);
+
 // ---- fused_mlp.hip
 bool ss_fused_mlp_fwd(const void* x, const void* desc, int M, int in_dim,
                       int nhidden, int cout, void* out, hipStream_t stream);

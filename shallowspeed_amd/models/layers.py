@@ -540,10 +540,117 @@ class Sequential(Module):
         self._fire_grad_hooks(lin)
         return dx
 
+    # width of the backward chain kernel (csrc/bwd_chain.hip) and the
+    # most ReLU layers one launch takes
+    _CHAIN_WIDTH = 256
+    _CHAIN_MAX_LAYERS = 8
+
+    def _bwd_chain_plan(self, mubatch_rows: int = 1):
+        """Which layers the backward chain kernel (F.bwd_chain) takes:
+        a list of (layer index, dgrad_in_chain), top layer first, or
+        None when the head or the layers under it do not qualify.
+
+        The chain is the fused head (Linear(256 -> C <= 16) +
+        SoftmaxXent) and the run of Linear(activation="relu") layers
+        with out_dims == 256 right below it.  A layer's dgrad is in the
+        chain when in_dims == 256 and its dx is needed; the chain ends
+        with the first layer whose dgrad is not (that layer still gets
+        its dz from the kernel), or above the first layer that is no
+        such Linear.  Looks at the layer configuration only — no
+        tensors, no device."""
+        pair = self._head_pair()
+        if pair is None or mubatch_rows < 1 or not F.bwd_chain_enabled() \
+                or not F.head_fused() or F.head_wgrad_fused():
+            return None
+        lin = pair[0]
+        if lin.in_dims != self._CHAIN_WIDTH or lin.out_dims > 16 \
+                or lin.fp8_fwd:
+            return None
+        plan = []
+        for i in range(len(self.layers) - 3, -1, -1):
+            layer = self.layers[i]
+            if len(plan) == self._CHAIN_MAX_LAYERS \
+                    or type(layer) is not Linear \
+                    or layer.activation != "relu" \
+                    or layer.out_dims != self._CHAIN_WIDTH:
+                break
+            need_dx = not (i == 0 and self._skip_input_grad)
+            in_chain = need_dx and layer.in_dims == self._CHAIN_WIDTH
+            if not in_chain and plan and not F.bwd_chain_dz_last():
+                break  # measured alternative: stop at dh of this layer
+            plan.append((i, in_chain))
+            if not in_chain:
+                break
+        return plan or None
+
+    def _wgrad_of(self, layer, dz, x):
+        """Unmasked weight gradient of `layer` from its dz: now, or kept
+        for the deferred flush (same window logic as Linear.backward)."""
+        if layer._defer_wgrad:
+            layer._wgrad_pending.append((dz, x, None))
+            if len(layer._wgrad_pending) >= layer._wgrad_window:
+                layer.flush_wgrad()
+        else:
+            F.linear_wgrad_acc(dz, x, layer.weight.grad, layer.bias.grad)
+
+    def _backward_chain(self, plan, lin, head, target, mubatch_id):
+        """Backward of the head pair and the planned ReLU layers through
+        ONE F.bwd_chain launch, then one unmasked wgrad per layer in the
+        per-layer order (head, then top to bottom), grad hooks fired
+        after each.  Returns (True, dx of the lowest planned layer), or
+        (False, None) with no stash touched when the tensors do not meet
+        the kernel's contract."""
+        s = head._cache.get(("s", mubatch_id))
+        x = lin._cache.get(("x", mubatch_id))
+        chain = [self.layers[i] for i, _ in plan]
+        hs = [l._cache.get(("y", mubatch_id)) for l in chain]
+        if s is None or x is None or any(h is None for h in hs) \
+                or not F.head_fused_ok(x, lin):
+            return False, None
+        if target.dtype != s.dtype:
+            target = target.to(s.dtype)
+        if not target.is_contiguous():
+            target = target.contiguous()
+        res = F.bwd_chain(
+            s, target, lin.weight.compute_t(), head.global_batch_size, hs,
+            [l.weight.compute_t() for l, (_, dg) in zip(chain, plan) if dg])
+        if res is None:
+            return False, None
+        dz_head, dzs, dx = res
+        # the chain kernel does not count: the standalone metrics launch
+        # reads the same probs / target (only when metrics are on)
+        if head._metrics is not None and head._training:
+            F.head_metrics(s, target, head._metrics, head.kind)
+        head._unstash("s", mubatch_id)
+        lin._unstash("x", mubatch_id)
+        self._wgrad_of(lin, dz_head, x)
+        self._fire_grad_hooks(head)
+        self._fire_grad_hooks(lin)
+        for layer, (i, dg), dz in zip(chain, plan, dzs):
+            xl = layer._unstash("x", mubatch_id)
+            layer._unstash("y", mubatch_id)
+            if not dg and not (i == 0 and self._skip_input_grad):
+                # the chain ended at this layer's dz but its dx is
+                # needed (in_dims != 256): the ordinary unmasked dgrad
+                dx = F.linear_dgrad(dz, layer.weight.compute(),
+                                    layer.weight.compute_t())
+            self._wgrad_of(layer, dz, xl)
+            self._fire_grad_hooks(layer)
+        return True, dx
+
     def backward(self, dout, mubatch_id: int = 0):
         d = dout
         last = len(self.layers) - 1
         pair = self._head_pair()
+        plan = self._bwd_chain_plan(dout.shape[0]) \
+            if pair and dout.is_cuda else None
+        if plan:
+            ok, dx = self._backward_chain(plan, pair[0], pair[1], d,
+                                          mubatch_id)
+            if ok:
+                d = dx
+                last = plan[-1][0] - 1
+                pair = None
         if pair:
             lin, head = pair
             x = lin._cache.get(("x", mubatch_id))

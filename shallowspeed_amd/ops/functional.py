@@ -91,6 +91,45 @@ def head_wgrad_fused() -> bool:
     return _HEAD_WGRAD_FUSED
 
 
+_BWD_CHAIN = None
+
+
+def set_bwd_chain(flag: bool):
+    """Run the head backward and the 256-wide ReLU layers' data
+    gradients below it as the one kernel of csrc/bwd_chain.hip (see
+    bwd_chain).  Every dz and dx keeps its bits; the weight gradients
+    then run unmasked on dz.  Default on; SS_BWD_CHAIN=0 (read once)
+    turns it off."""
+    global _BWD_CHAIN
+    _BWD_CHAIN = bool(flag)
+
+
+def bwd_chain_enabled() -> bool:
+    global _BWD_CHAIN
+    if _BWD_CHAIN is None:
+        import os
+
+        _BWD_CHAIN = os.environ.get("SS_BWD_CHAIN", "1") != "0"
+    return _BWD_CHAIN
+
+
+_BWD_CHAIN_DZ_LAST = None
+
+
+def bwd_chain_dz_last() -> bool:
+    """Whether the chain also takes a last layer whose dgrad it does not
+    run (the flagship's first layer), emitting that layer's dz so its
+    wgrad runs unmasked.  Off (SS_BWD_CHAIN_DZ1=0, read once: the
+    measured alternative), the chain ends at dh of that layer, which
+    keeps today's masked backward."""
+    global _BWD_CHAIN_DZ_LAST
+    if _BWD_CHAIN_DZ_LAST is None:
+        import os
+
+        _BWD_CHAIN_DZ_LAST = os.environ.get("SS_BWD_CHAIN_DZ1", "1") != "0"
+    return _BWD_CHAIN_DZ_LAST
+
+
 def _is_gpu(t: torch.Tensor) -> bool:
     return t.is_cuda
 
@@ -337,6 +376,36 @@ def head_bwd_fused(probs, target, x, w_t, global_batch, grad_w=None,
     if metrics is None:
         return tuple(_ext_for(probs).head_bwd_fused(*args))
     return tuple(_ext_for(probs).head_bwd_fused(*args, 0, metrics, 0))
+
+
+def bwd_chain(probs, target, w_head_t, global_batch, hs, w_ts, rows=0,
+              waves=0, w_lds=0):
+    """Head backward plus the ReLU-layer data gradients below it in one
+    kernel (GPU only, csrc/bwd_chain.hip).
+
+    hs: post-ReLU outputs of the chain's layers, top layer first (all
+    (M, 256)); w_ts: the transposed weights of the layers whose dgrad is
+    in the chain — all of them (dx of the last layer is returned) or all
+    but the last (the chain ends at dz of the last layer).
+
+      dz_head = (probs − target)/GB ;  dh = dz_head @ W_head
+      dz_l = dh ⊙ 1[h_l > 0] ;  dh = dz_l @ W_l ;  ...
+
+    Returns (dz_head, [dz_l, ...], dx or None), each bit-identical to
+    head_bwd_fused -> relu_bwd -> linear_dgrad -> ..., or None, with
+    nothing launched, when the inputs are outside the kernel's contract
+    (the caller takes the per-layer path).  rows / waves / w_lds select
+    the measured arms; 0 is the shipped choice."""
+    if not _is_gpu(probs):
+        return None
+    out = _ext_for(probs).bwd_chain(probs, target, w_head_t,
+                                    float(global_batch), list(hs),
+                                    list(w_ts), int(rows), int(waves),
+                                    int(w_lds))
+    if not out:
+        return None
+    n = len(hs)
+    return out[0], out[1:1 + n], (out[1 + n] if len(w_ts) == n else None)
 
 
 def xent_loss(probs, target, global_batch, eps=1e-9):
