@@ -72,6 +72,92 @@ torch::Tensor gemm_nt(torch::Tensor a, torch::Tensor b, torch::Tensor bias,
     return c;
 }
 
+// The mask constants as Python passes them (ops/functional.py computes
+// thr and scale, the one definition): every field is checked to fit its
+// 32 bits, and the launch's last row to stay a 32-bit sample id.
+DropoutArgs drop_args(int64_t key0, int64_t key1, int64_t step, int64_t layer,
+                      int64_t row_first, int64_t row_stride, int64_t thr,
+                      double scale, int64_t rows) {
+    auto u32 = [](int64_t v) { return v >= 0 && v <= (int64_t)UINT_MAX; };
+    TORCH_CHECK(u32(key0) && u32(key1) && u32(step) && u32(layer) &&
+                    u32(row_first) && u32(row_stride) && u32(thr),
+                "dropout: seed words, step, layer, rows and thr are 32-bit");
+    TORCH_CHECK(rows < 1 ||
+                    row_first + (rows - 1) * row_stride <= (int64_t)UINT_MAX,
+                "dropout: sample id past 2^32");
+    DropoutArgs d;
+    d.key0 = (unsigned)key0;
+    d.key1 = (unsigned)key1;
+    d.layer = (unsigned)layer;
+    d.step = (unsigned)step;
+    d.row_first = (unsigned)row_first;
+    d.row_stride = (unsigned)row_stride;
+    d.thr = (unsigned)thr;
+    d.scale = (float)scale;
+    return d;
+}
+
+// C = dropout(relu(a @ b^T + bias)): the fused epilogue where the shape's
+// tier has one, else gemm_nt followed by the in-place standalone pass
+// (also with fused = false, the measured alternative).
+torch::Tensor gemm_nt_dropout(torch::Tensor a, torch::Tensor b,
+                              torch::Tensor bias, int64_t key0, int64_t key1,
+                              int64_t step, int64_t layer, int64_t row_first,
+                              int64_t row_stride, int64_t thr, double scale,
+                              bool fused) {
+    check_bf16(a, "a");
+    check_bf16(b, "b");
+    check_bf16(bias, "bias");
+    TORCH_CHECK(a.dim() == 2 && b.dim() == 2, "a/b must be 2-D");
+    const int M = a.size(0), K = a.size(1), N = b.size(0);
+    TORCH_CHECK(b.size(1) == K, "K mismatch: ", K, " vs ", b.size(1));
+    TORCH_CHECK(bias.numel() == N, "bias size");
+    const DropoutArgs d = drop_args(key0, key1, step, layer, row_first,
+                                    row_stride, thr, scale, M);
+    auto c = torch::empty({M, N}, a.options());
+    if (fused)
+        fused = ss_gemm_nt_dropout(a.data_ptr(), b.data_ptr(),
+                                   bias.data_ptr(), c.data_ptr(), M, N, K, d,
+                                   cur_stream());
+    else
+        ss_gemm_nt(a.data_ptr(), b.data_ptr(), bias.data_ptr(), nullptr,
+                   c.data_ptr(), M, N, K, true, cur_stream());
+    if (!fused) ss_dropout_fwd(c.data_ptr(), M, N, d, cur_stream());
+    return c;
+}
+
+// y = dropout(y) in place on a finished post-ReLU activation.
+void dropout_fwd_(torch::Tensor y, int64_t key0, int64_t key1, int64_t step,
+                  int64_t layer, int64_t row_first, int64_t row_stride,
+                  int64_t thr, double scale) {
+    check_bf16(y, "y");
+    TORCH_CHECK(y.dim() == 2, "y must be 2-D");
+    const DropoutArgs d = drop_args(key0, key1, step, layer, row_first,
+                                    row_stride, thr, scale, y.size(0));
+    ss_dropout_fwd(y.data_ptr(), (int)y.size(0), (int)y.size(1), d,
+                   cur_stream());
+}
+
+// keep[r][c] (bool) for explicit int64 sample ids; the caller has checked
+// each id < 2^32.
+torch::Tensor dropout_keep_mask(torch::Tensor sample_ids, int64_t ncols,
+                                int64_t key0, int64_t key1, int64_t step,
+                                int64_t layer, int64_t thr) {
+    TORCH_CHECK(sample_ids.is_cuda() &&
+                    sample_ids.scalar_type() == torch::kLong &&
+                    sample_ids.dim() == 1 && sample_ids.is_contiguous(),
+                "sample_ids must be a contiguous CUDA int64 vector");
+    TORCH_CHECK(ncols >= 0 && ncols <= INT_MAX &&
+                    sample_ids.numel() <= INT_MAX, "mask too large");
+    const DropoutArgs d = drop_args(key0, key1, step, layer, 0, 1, thr, 1.0,
+                                    0);
+    auto keep = torch::empty({sample_ids.numel(), ncols},
+                             sample_ids.options().dtype(torch::kBool));
+    ss_dropout_mask(sample_ids.data_ptr(), keep.data_ptr(),
+                    (int)sample_ids.numel(), (int)ncols, d, cur_stream());
+    return keep;
+}
+
 // shared body of the two 256-tile wrappers; `tier` names it in the error
 torch::Tensor gemm_nt_256_tier(decltype(&ss_gemm_nt_256) launcher,
                                const char* tier, const torch::Tensor& a,
@@ -232,6 +318,17 @@ torch::Tensor relu_bwd(torch::Tensor dy, torch::Tensor y) {
     return dx;
 }
 
+torch::Tensor relu_bwd_scaled(torch::Tensor dy, torch::Tensor y,
+                              double scale) {
+    check_bf16(dy, "dy");
+    check_bf16(y, "y");
+    TORCH_CHECK(dy.sizes() == y.sizes(), "shape mismatch");
+    auto dx = torch::empty_like(dy);
+    ss_relu_bwd_scaled(dy.data_ptr(), y.data_ptr(), dx.data_ptr(), dy.numel(),
+                       (float)scale, cur_stream());
+    return dx;
+}
+
 torch::Tensor softmax_fwd(torch::Tensor x) {
     check_bf16(x, "x");
     TORCH_CHECK(x.dim() == 2, "x must be 2-D");
@@ -384,7 +481,7 @@ std::vector<torch::Tensor> bwd_chain(torch::Tensor probs, torch::Tensor target,
                                      std::vector<torch::Tensor> hs,
                                      std::vector<torch::Tensor> w_ts,
                                      int64_t rows, int64_t waves,
-                                     int64_t w_lds) {
+                                     int64_t w_lds, double dz_scale) {
     auto plain = [](const torch::Tensor& t) {
         return t.is_cuda() && t.scalar_type() == torch::kBFloat16 &&
                t.dim() == 2 && t.is_contiguous() &&
@@ -422,12 +519,20 @@ std::vector<torch::Tensor> bwd_chain(torch::Tensor probs, torch::Tensor target,
         out.push_back(torch::empty_like(hs[n - 1]));
         dx_p = out.back().data_ptr();
     }
-    if (!ss_bwd_chain(probs.data_ptr(), target.data_ptr(),
-                      w_head_t.data_ptr(), out[0].data_ptr(), hp, wp, dp,
-                      (int)n, dx_p, (int)M, (int)H, (int)C,
-                      (float)(1.0 / global_batch), (int)rows, (int)waves,
-                      (int)w_lds, cur_stream()))
-        return {};
+    // dz_scale 1.0 (no dropout) is today's unscaled kernel
+    const bool ok =
+        (float)dz_scale == 1.f
+            ? ss_bwd_chain(probs.data_ptr(), target.data_ptr(),
+                           w_head_t.data_ptr(), out[0].data_ptr(), hp, wp, dp,
+                           (int)n, dx_p, (int)M, (int)H, (int)C,
+                           (float)(1.0 / global_batch), (int)rows, (int)waves,
+                           (int)w_lds, cur_stream())
+            : ss_bwd_chain(probs.data_ptr(), target.data_ptr(),
+                           w_head_t.data_ptr(), out[0].data_ptr(), hp, wp, dp,
+                           (int)n, dx_p, (int)M, (int)H, (int)C,
+                           (float)(1.0 / global_batch), (int)rows, (int)waves,
+                           (int)w_lds, (float)dz_scale, cur_stream());
+    if (!ok) return {};
     return out;
 }
 
@@ -610,6 +715,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "chunked (deferred-µbatch) wgrad: one launch, many (dy,x) pairs");
     m.def("relu_fwd", &relu_fwd);
     m.def("relu_bwd", &relu_bwd);
+    m.def("relu_bwd_scaled", &relu_bwd_scaled,
+          "dz = bf16(dy * scale) where y > 0, else +0");
+    m.def("gemm_nt_dropout", &gemm_nt_dropout,
+          "C = dropout(relu(A @ B^T + bias)), mask in the GEMM epilogue",
+          py::arg("a"), py::arg("b"), py::arg("bias"), py::arg("key0"),
+          py::arg("key1"), py::arg("step"), py::arg("layer"),
+          py::arg("row_first"), py::arg("row_stride"), py::arg("thr"),
+          py::arg("scale"), py::arg("fused") = true);
+    m.def("dropout_fwd_", &dropout_fwd_,
+          "in-place dropout of a finished post-ReLU activation");
+    m.def("dropout_keep_mask", &dropout_keep_mask,
+          "keep bits (bool [M][ncols]) for explicit sample ids");
     m.def("softmax_fwd", &softmax_fwd);
     m.def("softmax_bwd", &softmax_bwd);
     m.def("head_mse_bwd", &head_mse_bwd);
@@ -628,7 +745,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "[dz_head, dz_l..., (dx)], or [] outside the contract",
           py::arg("probs"), py::arg("target"), py::arg("w_head_t"),
           py::arg("global_batch"), py::arg("hs"), py::arg("w_ts"),
-          py::arg("rows") = 0, py::arg("waves") = 0, py::arg("w_lds") = 0);
+          py::arg("rows") = 0, py::arg("waves") = 0, py::arg("w_lds") = 0,
+          py::arg("dz_scale") = 1.0);
     m.def("head_metrics", &head_metrics,
           "metric totals of (probs, target) into a slotted accumulator",
           py::arg("probs"), py::arg("target"), py::arg("acc"),

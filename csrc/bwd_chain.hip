@@ -57,7 +57,12 @@ struct BwdChainLayers {
 // 32-wide K-chunks (register-staged, double-buffered, one barrier per
 // K-step, as gemm_nt_kernel stages B) instead of L2 -> registers; the
 // measured alternative (85 KB of LDS: one block per CU).
-template <int R, int NW, bool WLDS>
+// SCALED: the layers ran inverted dropout, so a kept dz element is
+// bf16(dh · dz_scale) with dz_scale = 1/keep, one value for the launch
+// (the stashed h already is the mask: h > 0 ⇔ z > 0 ∧ kept).  SA is that
+// float: an EMPTY pack when not SCALED, so those instantiations keep
+// their kernel arguments and code.
+template <int R, int NW, bool WLDS, bool SCALED = false, class... SA>
 __global__ __launch_bounds__(NW * 64, WLDS ? NW / 4 : NW / 2)
 void bwd_chain_kernel(
     const __bf16* __restrict__ probs,    // [M][C]
@@ -66,7 +71,8 @@ void bwd_chain_kernel(
     __bf16* __restrict__ dz_head,        // [M][C]
     const BwdChainLayers L, int nlayers,
     __bf16* __restrict__ dx,             // [M][256] or null
-    int M, int C, float inv_gb, int ntiles) {
+    int M, int C, float inv_gb, int ntiles, SA... dz_scale) {
+    static_assert(sizeof...(SA) == SCALED, "one dz_scale when SCALED");
     constexpr int H = 256;
     constexpr int NT = NW * 64;
     constexpr int LDT = H + 8;          // padded tile row (bf16)
@@ -152,8 +158,11 @@ void bwd_chain_kernel(
                 const int r = q / PPR, col = (q % PPR) * 8;
                 bf16x8 v = *(const bf16x8*)&tile[r][col];
 #pragma unroll
-                for (int e = 0; e < 8; ++e)
+                for (int e = 0; e < 8; ++e) {
                     if (!(bf2f(hm[i][e]) > 0.f)) v[e] = (__bf16)0.f;
+                    else if constexpr (SCALED)
+                        v[e] = f2bf(bf2f(v[e]) * (dz_scale + ...));
+                }
                 *(bf16x8*)&tile[r][col] = v;
                 if (row0 + r < M)
                     *(gbf16x8*)&dzo[(long)(row0 + r) * H + col] = v;
@@ -301,6 +310,20 @@ void bwd_chain_launch(const void* probs, const void* target,
                        (__bf16*)dx, M, C, inv_gb, ntiles);
 }
 
+// the shipped arm with scaled dz
+void bwd_chain_launch_scaled(const void* probs, const void* target,
+                             const void* Wt_head, void* dz_head,
+                             const BwdChainLayers& L, int nlayers, void* dx,
+                             int M, int C, float inv_gb, float dz_scale,
+                             hipStream_t st) {
+    const int ntiles = cdiv(M, 64);
+    hipLaunchKernelGGL((bwd_chain_kernel<64, 8, false, true, float>),
+                       dim3(ntiles), dim3(8 * 64), 0, st,
+                       (const __bf16*)probs, (const __bf16*)target,
+                       (const __bf16*)Wt_head, (__bf16*)dz_head, L, nlayers,
+                       (__bf16*)dx, M, C, inv_gb, ntiles, dz_scale);
+}
+
 }  // namespace
 
 // rows / waves: 0 = the shipped choice (64, 8); (32, 4), (32, 8),
@@ -309,11 +332,14 @@ void bwd_chain_launch(const void* probs, const void* target,
 // registers), 1 = W^T through LDS, built for (64, 8) only.
 // SS_BWD_CHAIN_ROWS / SS_BWD_CHAIN_WAVES / SS_BWD_CHAIN_WLDS (read once)
 // override the shipped choice for tuning.
-bool ss_bwd_chain(const void* probs, const void* target, const void* Wt_head,
-                  void* dz_head, const void* const* h, const void* const* wt,
-                  void* const* dz, int nlayers, void* dx, int M, int H, int C,
-                  float inv_gb, int rows, int waves, int w_lds,
-                  hipStream_t st) {
+// scaled: dz_scale applies (any value, 1.0 included); only the shipped
+// arm is built with it.
+static bool bwd_chain_any(const void* probs, const void* target,
+                          const void* Wt_head, void* dz_head,
+                          const void* const* h, const void* const* wt,
+                          void* const* dz, int nlayers, void* dx, int M, int H,
+                          int C, float inv_gb, int rows, int waves, int w_lds,
+                          bool scaled, float dz_scale, hipStream_t st) {
     if (M < 1 || H != 256 || C < 1 || C > 16 || nlayers < 1 ||
         nlayers > SS_BWD_CHAIN_MAX)
         return false;
@@ -333,6 +359,12 @@ bool ss_bwd_chain(const void* probs, const void* target, const void* Wt_head,
     if (!waves) waves = env_waves ? env_waves : 8;
     static const int env_wlds = env_int("SS_BWD_CHAIN_WLDS", 0);
     if (!w_lds) w_lds = env_wlds;
+    if (scaled) {
+        if (rows != 64 || waves != 8 || w_lds != 0) return false;
+        bwd_chain_launch_scaled(probs, target, Wt_head, dz_head, L, nlayers,
+                                dx, M, C, inv_gb, dz_scale, st);
+        return true;
+    }
     if (w_lds == 1) {
         if (rows != 64 || waves != 8) return false;
         bwd_chain_launch<64, 8, true>(probs, target, Wt_head, dz_head, L,
@@ -354,4 +386,24 @@ bool ss_bwd_chain(const void* probs, const void* target, const void* Wt_head,
     else
         return false;
     return true;
+}
+
+bool ss_bwd_chain(const void* probs, const void* target, const void* Wt_head,
+                  void* dz_head, const void* const* h, const void* const* wt,
+                  void* const* dz, int nlayers, void* dx, int M, int H, int C,
+                  float inv_gb, int rows, int waves, int w_lds,
+                  hipStream_t st) {
+    return bwd_chain_any(probs, target, Wt_head, dz_head, h, wt, dz, nlayers,
+                         dx, M, H, C, inv_gb, rows, waves, w_lds, false, 1.f,
+                         st);
+}
+
+bool ss_bwd_chain(const void* probs, const void* target, const void* Wt_head,
+                  void* dz_head, const void* const* h, const void* const* wt,
+                  void* const* dz, int nlayers, void* dx, int M, int H, int C,
+                  float inv_gb, int rows, int waves, int w_lds,
+                  float dz_scale, hipStream_t st) {
+    return bwd_chain_any(probs, target, Wt_head, dz_head, h, wt, dz, nlayers,
+                         dx, M, H, C, inv_gb, rows, waves, w_lds, true,
+                         dz_scale, st);
 }

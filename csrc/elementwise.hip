@@ -18,6 +18,7 @@
 // Guideline 13), f32 math internally, wave-shuffle row reductions.
 
 #include "common.h"
+#include "dropout_dev.h"
 #include "launchers.h"
 
 // ------------------------------------------------------------- relu
@@ -61,6 +62,102 @@ __global__ __launch_bounds__(256) void relu_bwd_kernel(
     if (i < n) {
         for (; i < n; ++i)
             dx[i] = bf2f(y[i]) > 0.f ? dy[i] : (__bf16)0.f;
+    }
+}
+
+// ReLU backward under inverted dropout: the stashed output y is
+// relu(z)·m/keep, so y > 0 ⇔ z > 0 ∧ m = 1 and dz = bf16(dy·scale) there,
+// +0 elsewhere.  Same mask rule as relu_bwd_kernel (NaN and −0.0 in y
+// mask to +0).
+__global__ __launch_bounds__(256) void relu_bwd_scaled_kernel(
+    const __bf16* __restrict__ dy, const __bf16* __restrict__ y,
+    __bf16* __restrict__ dx, long n, float scale) {
+    long i = (long)(blockIdx.x * 256 + threadIdx.x) * 8;
+    const long stride = (long)gridDim.x * 256 * 8;
+    for (; i + 8 <= n; i += stride) {
+        bf16x8 g = *(const bf16x8*)(dy + i);
+        bf16x8 m = *(const bf16x8*)(y + i);
+        bf16x8 o;
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+            o[j] = bf2f(m[j]) > 0.f ? f2bf(bf2f(g[j]) * scale) : (__bf16)0.f;
+        *(bf16x8*)(dx + i) = o;
+    }
+    if (i < n) {
+        for (; i < n; ++i)
+            dx[i] = bf2f(y[i]) > 0.f ? f2bf(bf2f(dy[i]) * scale)
+                                     : (__bf16)0.f;
+    }
+}
+
+// ------------------------------------------------------------- dropout
+
+// The mask of dropout_dev.h applied IN PLACE to a finished post-ReLU
+// bf16 activation [M][N]: the forward of the GEMM tiers without the
+// fused epilogue.  Same keep bits as the epilogue; a kept value is
+// bf16(float(y)·scale), rounded a second time, so it may differ from
+// the fused path's single rounding by one bf16 ulp.
+// N % 8 == 0: one thread per 8 columns (16-B load and store, two Philox
+// calls), grid-strided over the M·N/8 pieces.
+__global__ __launch_bounds__(256) void dropout_fwd_kernel(
+    __bf16* __restrict__ y, int M, int N, const DropoutArgs d) {
+    const int ppr = N / 8;
+    const long npieces = (long)M * ppr;
+    long q = (long)blockIdx.x * 256 + threadIdx.x;
+    const long stride = (long)gridDim.x * 256;
+    for (; q < npieces; q += stride) {
+        const int row = (int)(q / ppr), col = (int)(q % ppr) * 8;
+        bf16x8 v = *(const bf16x8*)(y + (long)row * N + col);
+        const unsigned s = dropout_sample(d, row);
+        const unsigned keep = dropout_keep4(d, s, (unsigned)col >> 2) |
+                              (dropout_keep4(d, s, ((unsigned)col >> 2) + 1)
+                               << 4);
+#pragma unroll
+        for (int e = 0; e < 8; ++e)
+            v[e] = (keep >> e) & 1 ? f2bf(bf2f(v[e]) * d.scale)
+                                   : (__bf16)0.f;
+        *(bf16x8*)(y + (long)row * N + col) = v;
+    }
+}
+
+// any N: one thread per 4-column group, scalar accesses, columns past N
+// guarded
+__global__ __launch_bounds__(256) void dropout_fwd_ragged_kernel(
+    __bf16* __restrict__ y, int M, int N, const DropoutArgs d) {
+    const int gpr = (N + 3) / 4;
+    const long ngroups = (long)M * gpr;
+    long q = (long)blockIdx.x * 256 + threadIdx.x;
+    const long stride = (long)gridDim.x * 256;
+    for (; q < ngroups; q += stride) {
+        const int row = (int)(q / gpr), cg = (int)(q % gpr);
+        const unsigned keep = dropout_keep4(d, dropout_sample(d, row), cg);
+        for (int e = 0; e < 4; ++e) {
+            const int col = cg * 4 + e;
+            if (col >= N) break;
+            __bf16* p = y + (long)row * N + col;
+            *p = (keep >> e) & 1 ? f2bf(bf2f(*p) * d.scale) : (__bf16)0.f;
+        }
+    }
+}
+
+// The keep bits themselves, for tests and host-side checks: keep[r][c]
+// (one byte, 0 / 1) for explicit 64-bit sample ids (each < 2^32, checked
+// by the caller).  row_first / row_stride of d are not used.
+__global__ __launch_bounds__(256) void dropout_mask_kernel(
+    const long* __restrict__ sample_ids, unsigned char* __restrict__ keep,
+    int M, int N, const DropoutArgs d) {
+    const int gpr = (N + 3) / 4;
+    const long ngroups = (long)M * gpr;
+    long q = (long)blockIdx.x * 256 + threadIdx.x;
+    const long stride = (long)gridDim.x * 256;
+    for (; q < ngroups; q += stride) {
+        const int row = (int)(q / gpr), cg = (int)(q % gpr);
+        const unsigned k = dropout_keep4(d, (unsigned)sample_ids[row], cg);
+        for (int e = 0; e < 4; ++e) {
+            const int col = cg * 4 + e;
+            if (col >= N) break;
+            keep[(long)row * N + col] = (k >> e) & 1;
+        }
     }
 }
 
@@ -233,6 +330,42 @@ void ss_relu_bwd(const void* dy, const void* y, void* dx, long n,
                  hipStream_t st) {
     hipLaunchKernelGGL(relu_bwd_kernel, dim3(ew_grid(n)), dim3(256), 0, st,
                        (const __bf16*)dy, (const __bf16*)y, (__bf16*)dx, n);
+}
+
+void ss_relu_bwd_scaled(const void* dy, const void* y, void* dx, long n,
+                        float scale, hipStream_t st) {
+    hipLaunchKernelGGL(relu_bwd_scaled_kernel, dim3(ew_grid(n)), dim3(256), 0,
+                       st, (const __bf16*)dy, (const __bf16*)y, (__bf16*)dx, n,
+                       scale);
+}
+
+// grid of the dropout kernels: one thread per work item, grid-strided
+// past 2048 blocks
+static int drop_grid(long items) {
+    long blocks = (items + 255) / 256;
+    return (int)(blocks < 1 ? 1 : blocks > 2048 ? 2048 : blocks);
+}
+
+void ss_dropout_fwd(void* y, int M, int N, const DropoutArgs& drop,
+                    hipStream_t st) {
+    if (M < 1 || N < 1) return;
+    if (N % 8 == 0 && ((uintptr_t)y & 15) == 0)
+        hipLaunchKernelGGL(dropout_fwd_kernel,
+                           dim3(drop_grid((long)M * (N / 8))), dim3(256), 0,
+                           st, (__bf16*)y, M, N, drop);
+    else
+        hipLaunchKernelGGL(dropout_fwd_ragged_kernel,
+                           dim3(drop_grid((long)M * ((N + 3) / 4))),
+                           dim3(256), 0, st, (__bf16*)y, M, N, drop);
+}
+
+void ss_dropout_mask(const void* sample_ids, void* keep, int M, int N,
+                     const DropoutArgs& drop, hipStream_t st) {
+    if (M < 1 || N < 1) return;
+    hipLaunchKernelGGL(dropout_mask_kernel,
+                       dim3(drop_grid((long)M * ((N + 3) / 4))), dim3(256), 0,
+                       st, (const long*)sample_ids, (unsigned char*)keep, M, N,
+                       drop);
 }
 
 void ss_softmax_fwd(const void* x, void* s, int B, int C, hipStream_t st) {

@@ -21,20 +21,41 @@
 //     M/N/K (full bounds handling) — launch count, not MFMA peak, is
 //     the budget here.
 
+#include "dropout_dev.h"
 #include "launchers.h"
 #include "stage_reg.h"
 
 // ---------------------------------------------------------------- gemm_nt
 
+__device__ __forceinline__ const DropoutArgs& drop_args(const DropoutArgs& d) {
+    return d;
+}
+
+// DROPOUT (valid only with HAS_BIAS && RELU && !HAS_MASK): the
+// inverted-dropout mask of dropout_dev.h applied to the f32 value before
+// its one rounding to bf16, v = keep ? relu(acc + b) * scale : +0.
+// One Philox call per 16x16 fragment and lane: a call yields four
+// consecutive columns of one sample; in the MFMA C layout those are the
+// four lanes of a quad (lane & ~3 .. +3), each holding rows r = 0..3 of
+// its column.  Lane q of the quad runs the call of row q, and the quad
+// exchanges the four keep bits with DPP quad_perm broadcasts.  (A call
+// per element, four per fragment and lane, measured 17.2 against 10.6 µs
+// at the flagship hidden forward: profiles/r08_dropout.md.)
+// DA is the DropoutArgs block: an EMPTY pack with DROPOUT off, so those
+// instantiations keep their kernel arguments and code.
 template <int BM, int BN, int KSTEP, int WAVES_M, int WAVES_N,
-          bool HAS_BIAS, bool RELU, bool HAS_MASK>
+          bool HAS_BIAS, bool RELU, bool HAS_MASK, bool DROPOUT = false,
+          class... DA>
 __global__ __launch_bounds__(WAVES_M * WAVES_N * 64) void gemm_nt_kernel(
     const __bf16* __restrict__ A,     // [M][K]
     const __bf16* __restrict__ B,     // [N][K]
     const __bf16* __restrict__ bias,  // [N]
     const __bf16* __restrict__ mask,  // [M][K] (A-mask source, >0 keeps)
     __bf16* __restrict__ C,           // [M][N]
-    int M, int N, int K) {
+    int M, int N, int K, DA... da) {
+    static_assert(sizeof...(DA) == DROPOUT, "one DropoutArgs block");
+    static_assert(!DROPOUT || (HAS_BIAS && RELU && !HAS_MASK),
+                  "dropout is an epilogue of the bias+ReLU forward");
     constexpr int WM = BM / WAVES_M;        // wave tile rows
     constexpr int WN = BN / WAVES_N;        // wave tile cols
     constexpr int FM = WM / 16;             // 16x16 frags per wave (M)
@@ -120,6 +141,27 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64) void gemm_nt_kernel(
 #pragma unroll
         for (int j = 0; j < FN; ++j) {
             const int gcol = n0 + wn * WN + j * 16 + lrow;
+            unsigned keep4 = 0;  // bit r: row r of this lane's column kept
+            if constexpr (DROPOUT) {
+                // before any lane leaves: the exchange needs the whole
+                // quad.  The tile origins are multiples of 16, so the
+                // quad shares gcol >> 2 and lane & 3 == gcol & 3.
+                const DropoutArgs& d = drop_args(da...);
+                const int q = lane & 3;
+                const unsigned mine = dropout_keep4(
+                    d, dropout_sample(d, m0 + wm * WM + i * 16 + kch * 4 + q),
+                    (unsigned)gcol >> 2);
+                const unsigned b0 = __builtin_amdgcn_update_dpp(
+                    0, (int)mine, 0x00, 0xf, 0xf, true);
+                const unsigned b1 = __builtin_amdgcn_update_dpp(
+                    0, (int)mine, 0x55, 0xf, 0xf, true);
+                const unsigned b2 = __builtin_amdgcn_update_dpp(
+                    0, (int)mine, 0xaa, 0xf, 0xf, true);
+                const unsigned b3 = __builtin_amdgcn_update_dpp(
+                    0, (int)mine, 0xff, 0xf, 0xf, true);
+                keep4 = ((b0 >> q) & 1) | (((b1 >> q) & 1) << 1) |
+                        (((b2 >> q) & 1) << 2) | (((b3 >> q) & 1) << 3);
+            }
             if (gcol >= N) continue;
             float bv = 0.f;
             if constexpr (HAS_BIAS) bv = bf2f(bias[gcol]);
@@ -130,6 +172,8 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64) void gemm_nt_kernel(
                 float v = acc[i][j][r];
                 if constexpr (HAS_BIAS) v += bv;
                 if constexpr (RELU) v = v > 0.f ? v : 0.f;
+                if constexpr (DROPOUT)
+                    v = (keep4 >> r) & 1 ? v * drop_args(da...).scale : 0.f;
                 C[(long)grow * N + gcol] = f2bf(v);
             }
         }
@@ -343,9 +387,14 @@ __global__ __launch_bounds__(256) void colsum_kernel(
 
 // ---------------------------------------------------------------- launchers
 
-void ss_gemm_nt(const void* A, const void* B, const void* bias,
-                const void* mask, void* C, int M, int N, int K,
-                bool relu, hipStream_t stream) {
+// The tier ladder of every gemm_nt launch.  drop != null (bias + ReLU
+// forward under dropout, no mask): the register-staged tiers run the
+// mask in their epilogue and the function returns true; the 256-tile and glds tiers run as they are and
+// it returns false — the caller owes the standalone pass.
+static bool gemm_nt_dispatch(const void* A, const void* B, const void* bias,
+                             const void* mask, void* C, int M, int N, int K,
+                             bool relu, const DropoutArgs* drop,
+                             hipStream_t stream) {
     const bool has_bias = bias != nullptr;
     const bool has_mask = mask != nullptr;
 
@@ -365,6 +414,15 @@ void ss_gemm_nt(const void* A, const void* B, const void* bias,
         constexpr int WAVES_N = BM == 32 ? 4 : 2;
         dim3 block(WAVES_M * WAVES_N * 64);
         dim3 grid(cdiv(M, BM), cdiv(N, BN));
+        if (drop) {
+            hipLaunchKernelGGL(
+                (gemm_nt_kernel<BM, BN, 32, WAVES_M, WAVES_N, true, true,
+                                false, true, DropoutArgs>),
+                grid, block, 0, stream, (const __bf16*)A, (const __bf16*)B,
+                (const __bf16*)bias, (const __bf16*)nullptr, (__bf16*)C, M, N,
+                K, *drop);
+            return;
+        }
         with_bools(
             [&](auto hb, auto rl, auto hm) {
                 // Measured: KSTEP=64 is throughput-neutral at these
@@ -393,7 +451,7 @@ void ss_gemm_nt(const void* A, const void* B, const void* bias,
     if (!has_mask && N >= 512 && (long)(M / 256) * (N / 256) >= 128) {
         static const int en256 = env_int("SS_GEMM256", 1);
         if (en256 && ss_gemm_nt_256(A, B, bias, C, M, N, K, relu, stream))
-            return;
+            return false;
     }
     // compute-bound tier: aligned shapes with no fused mask go to the
     // glds-staged kernel (direct HBM->LDS DMA)
@@ -408,7 +466,7 @@ void ss_gemm_nt(const void* A, const void* B, const void* bias,
                     (__bf16*)C, M, N, K);
             },
             has_bias, relu);
-        return;
+        return false;
     }
     // 128x128 only when the grid still covers the CUs with >=2
     // blocks each (1 block/CU = 4 waves starves latency hiding)
@@ -422,6 +480,20 @@ void ss_gemm_nt(const void* A, const void* B, const void* bias,
     } else {
         launch(B64{});
     }
+    return drop != nullptr;
+}
+
+void ss_gemm_nt(const void* A, const void* B, const void* bias,
+                const void* mask, void* C, int M, int N, int K,
+                bool relu, hipStream_t stream) {
+    gemm_nt_dispatch(A, B, bias, mask, C, M, N, K, relu, nullptr, stream);
+}
+
+bool ss_gemm_nt_dropout(const void* A, const void* B, const void* bias,
+                        void* C, int M, int N, int K,
+                        const DropoutArgs& drop, hipStream_t stream) {
+    return gemm_nt_dispatch(A, B, bias, nullptr, C, M, N, K, true, &drop,
+                            stream);
 }
 
 void ss_colsum(const void* dY, const void* mask, void* gb, int M, int N,

@@ -20,6 +20,24 @@ void ss_gemm_nt(const void* A, const void* B, const void* bias,
 void ss_colsum(const void* dY, const void* mask, void* gb, int M, int N,
                hipStream_t stream);
 
+// Launch-constant part of the dropout mask (dropout_dev.h), passed by
+// value to the kernels.  Row i of a launch is sample
+// row_first + i * row_stride (32-bit).
+struct DropoutArgs {
+    unsigned key0, key1;   // seed low / high word
+    unsigned layer, step;  // counter words 2, 3
+    unsigned row_first, row_stride;
+    unsigned thr;          // keep when word < thr
+    float scale;           // float32(1 / (1 - p))
+};
+// C = dropout(relu(A · B^T + bias)) with the mask in the GEMM epilogue.
+// bias is required.  Returns false when the
+// shape's tier has no fused epilogue (256-tile, glds): C then holds the
+// plain relu(A · B^T + bias) and the caller runs ss_dropout_fwd on it.
+bool ss_gemm_nt_dropout(const void* A, const void* B, const void* bias,
+                        void* C, int M, int N, int K,
+                        const DropoutArgs& drop, hipStream_t stream);
+
 // ---- gemm256.hip / gemm256w.hip
 bool ss_gemm_nt_256(const void* A, const void* B, const void* bias, void* C,
                     int M, int N, int K, bool relu, hipStream_t stream);
@@ -66,6 +84,13 @@ bool ss_bwd_chain(const void* probs, const void* target, const void* Wt_head,
                   void* const* dz, int nlayers, void* dx, int M, int H, int C,
                   float inv_gb, int rows, int waves, int w_lds,
                   hipStream_t stream);
+// The same with every dz_l scaled by dz_scale (inverted dropout's
+// 1/keep); built for the shipped arm only, false for the others.
+bool ss_bwd_chain(const void* probs, const void* target, const void* Wt_head,
+                  void* dz_head, const void* const* h, const void* const* wt,
+                  void* const* dz, int nlayers, void* dx, int M, int H, int C,
+                  float inv_gb, int rows, int waves, int w_lds,
+                  float dz_scale, hipStream_t stream);
 
 // ---- fused_mlp.hip
 bool ss_fused_mlp_fwd(const void* x, const void* desc, int M, int in_dim,
@@ -75,6 +100,12 @@ bool ss_fused_mlp_fwd(const void* x, const void* desc, int M, int in_dim,
 void ss_relu_fwd(const void* x, void* y, long n, hipStream_t stream);
 void ss_relu_bwd(const void* dy, const void* y, void* dx, long n,
                  hipStream_t stream);
+void ss_relu_bwd_scaled(const void* dy, const void* y, void* dx, long n,
+                        float scale, hipStream_t stream);
+void ss_dropout_fwd(void* y, int M, int N, const DropoutArgs& drop,
+                    hipStream_t stream);
+void ss_dropout_mask(const void* sample_ids, void* keep, int M, int N,
+                     const DropoutArgs& drop, hipStream_t stream);
 void ss_softmax_fwd(const void* x, void* s, int B, int C, hipStream_t stream);
 void ss_softmax_bwd(const void* dy, const void* s, void* dx, int B, int C,
                     hipStream_t stream);

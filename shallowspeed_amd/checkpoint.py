@@ -10,13 +10,17 @@ assert_sync).  Layout:
     <dir>/meta.pt                      (world/dp/pp, sizes, step)
     <dir>/stage_{s:02d}.pt             (f32 master params + optimizer
                                         state — momentum velocities —
-                                        in parameter order)
+                                        in parameter order; the dropout
+                                        seed and step counter)
 
 Resuming a momentum>0 run restores the exact optimization trajectory
 (velocities + hyperparameters are saved with the stage shard); loading
 validates the checkpoint's PP/TP topology against the current one so a
 repartitioned resume fails loudly instead of via per-tensor shape
-asserts alone.  TP shards write one file per TP rank
+asserts alone.  The dropout mask is keyed on (seed, step, ...), so the
+shard carries both and a resumed run continues the mask sequence; a
+shard without them (written before dropout existed) loads as step 0 and
+keeps the model's seed.  TP shards write one file per TP rank
 (stage_XX_tpYY.pt).  If ranks load a checkpoint IMMEDIATELY after a
 collective save in the same run, put a dist.barrier() between save and
 load — rank 0 writes meta.pt and other ranks must not race it (the
@@ -46,6 +50,9 @@ def save_checkpoint(path, model, topo, step: int = 0, extra=None,
             "stage_id": topo.stage_id,
             "step": step,
         }
+        if hasattr(model, "dropout_step"):
+            state["dropout"] = {"seed": model.dropout_seed,
+                                "step": model.dropout_step}
         if optimizer is not None and hasattr(optimizer, "state_dict"):
             opt_state = optimizer.state_dict()
             # stateless SGD (no momentum): nothing worth persisting
@@ -85,6 +92,11 @@ def load_checkpoint(path, model, topo, optimizer=None):
         assert p.data.shape == saved.shape, (p.data.shape, saved.shape)
         p.data.copy_(saved.to(p.data.device))
         p.sync_lp()
+    if hasattr(model, "dropout_step"):
+        drop = state.get("dropout", {})
+        model.dropout_step = drop.get("step", 0)
+        if "seed" in drop:
+            model.dropout_seed = drop["seed"]
     if optimizer is not None and "opt" in state:
         optimizer.load_state_dict(state["opt"])
     return meta

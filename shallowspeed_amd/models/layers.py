@@ -140,8 +140,36 @@ class Module:
             p.materialize_device(device, compute_dtype)
 
 
+class DropoutState:
+    """What the dropout mask depends on besides the layer and the
+    element (F.dropout_keep_mask): the 64-bit seed, the number of
+    optimizer steps taken, and per µbatch the sample ids of its rows as
+    (first, stride) — row i of µbatch m is sample first + i·stride of
+    the unsharded dataset order.  One object per Sequential, shared by
+    its Linears; a hand-driven Linear owns a default one (seed 0, step
+    0, rows 0, 1, 2, ...)."""
+
+    def __init__(self, seed: int = 0):
+        self.seed = int(seed)
+        self.step = 0
+        self.rows = {}
+
+    def sample_rows(self, mubatch_id):
+        return self.rows.get(mubatch_id, (0, 1))
+
+
 class Linear(Module):
     """y = x @ W^T + b with optional FUSED ReLU (GEMM epilogue).
+
+    dropout=p (0 <= p < 1, ReLU layers only): inverted dropout on the
+    ReLU output in training mode, y = relu(z)·m/(1−p), with the
+    counter-based mask of F.dropout_keep_mask keyed on (seed, step,
+    layer_index, sample, column) — on GPU in the forward GEMM's
+    epilogue.  Only ReLU, because the stashed output then already is the
+    backward's mask (y>0 ⟺ z>0 ∧ m=1): dz = dh ⊙ 1[y>0]/(1−p), no mask
+    and no RNG kept.  layer_index is the Linear's index in the full
+    model, so pipeline stage slicing does not change the bits.  In eval
+    mode, or with p = 0, the forward is exactly the call without it.
 
     Reference: layers.py:99-142 (module-level ReLU fusion at
     layers.py:120-122 becomes a kernel epilogue; backward unwinds the
@@ -151,11 +179,25 @@ class Linear(Module):
     (layers.py:106-113).
     """
 
-    def __init__(self, in_dims: int, out_dims: int, activation=None):
+    def __init__(self, in_dims: int, out_dims: int, activation=None,
+                 dropout: float = 0.0, layer_index: int = 0):
         super().__init__()
         assert activation in (None, "relu", "gelu")
+        dropout = float(dropout)
+        if not 0.0 <= dropout < 1.0:
+            raise ValueError(f"dropout must be in [0, 1), got {dropout}")
+        if dropout > 0.0 and activation != "relu":
+            raise ValueError(
+                "dropout needs activation='relu': the post-ReLU output "
+                "doubles as the backward mask (y > 0 <=> kept and active)")
         self.in_dims, self.out_dims = in_dims, out_dims
         self.activation = activation
+        self.dropout = dropout
+        self.layer_index = int(layer_index)
+        self._drop_state = DropoutState()  # Sequential shares its own
+        if dropout > 0.0:
+            self.forward = self._forward_dropout
+            self.backward = self._backward_dropout
         g = torch.Generator().manual_seed(_shape_seed(in_dims, out_dims))
         w = torch.randn(out_dims, in_dims, generator=g, dtype=torch.float32)
         w /= math.sqrt(in_dims)
@@ -187,6 +229,21 @@ class Linear(Module):
         return (self.fp8_fwd and self.activation in (None, "relu")
                 and rows % 256 == 0
                 and self.out_dims % 256 == 0 and self.in_dims % 256 == 0)
+
+    def _drop_on(self) -> bool:
+        return self.dropout > 0.0 and self._training
+
+    def dz_scale(self) -> float:
+        """What the backward multiplies kept gradients by: float32
+        1/(1−p) under dropout, else 1."""
+        return F.dropout_params(self.dropout)[1] if self._drop_on() else 1.0
+
+    def _drop_key(self, mubatch_id):
+        """(seed, step, layer, row_first, row_stride, p) of this forward."""
+        st = self._drop_state
+        first, stride = st.sample_rows(mubatch_id)
+        return (st.seed, st.step, self.layer_index, first, stride,
+                self.dropout)
 
     def forward(self, inputs, mubatch_id: int = 0):
         self._stash("x", mubatch_id, inputs)
@@ -266,6 +323,49 @@ class Linear(Module):
         else:
             F.linear_wgrad_acc(dout, x, self.weight.grad, self.bias.grad,
                                mask_src)
+        return dx
+
+    # ---- dropout: bound over forward / backward per INSTANCE when
+    # dropout > 0 (see __init__), so a layer without it runs the two
+    # methods above and nothing else
+    def _forward_dropout(self, inputs, mubatch_id: int = 0):
+        if not self._training:
+            return Linear.forward(self, inputs, mubatch_id)
+        self._stash("x", mubatch_id, inputs)
+        key = self._drop_key(mubatch_id)
+        if inputs.is_cuda and self._fp8_ok(inputs.shape[0]):
+            # the fp8 tier has no dropout epilogue: standalone pass
+            if self._wq is None:
+                self._wq, self._ws = F.fp8_quantize(self.weight.compute())
+            xq, xs = F.fp8_quantize(inputs)
+            y = F.linear_fwd_fp8(xq, xs, self._wq, self._ws,
+                                 self.bias.compute(), relu=True)
+            F.dropout_fwd_(y, *key)
+        else:
+            y = F.linear_fwd_dropout(inputs, self.weight.compute(),
+                                     self.bias.compute(), *key)
+        # the post-dropout output is the backward's mask source
+        self._stash("y", mubatch_id, y)
+        return y
+
+    def _backward_dropout(self, dout, mubatch_id: int = 0,
+                          need_dx: bool = True):
+        x = self._unstash("x", mubatch_id)
+        y = self._unstash("y", mubatch_id)
+        # dz = dout ⊙ 1[y>0]/(1−p), materialised once; dgrad and wgrad
+        # then run unmasked (the masked-operand kernels carry no scale)
+        # — the path wide layers take anyway
+        dz = F.relu_bwd(dout, y, scale=self.dz_scale())
+        dx = None
+        if need_dx:
+            dx = F.linear_dgrad(dz, self.weight.compute(),
+                                self.weight.compute_t())
+        if self._defer_wgrad:
+            self._wgrad_pending.append((dz, x, None))
+            if len(self._wgrad_pending) >= self._wgrad_window:
+                self.flush_wgrad()
+        else:
+            F.linear_wgrad_acc(dz, x, self.weight.grad, self.bias.grad)
         return dx
 
     def flush_wgrad(self):
@@ -444,6 +544,15 @@ class Sequential(Module):
     def __init__(self, layers):
         super().__init__()
         self.layers = list(layers)
+        # dropout state shared by every Linear of the chain; whether any
+        # layer drops is fixed here, so the p = 0 hot path pays one
+        # attribute test for the feature
+        self._dropout = DropoutState()
+        for layer in self.layers:
+            if isinstance(layer, Linear):
+                layer._drop_state = self._dropout
+        self._has_dropout = any(getattr(l, "dropout", 0.0) > 0.0
+                                for l in self.layers)
         self._grad_hooks = []
         self._post_grad_hooks = []
         # set True on pipeline stage 0: the first Linear's input grad is
@@ -463,6 +572,34 @@ class Sequential(Module):
     # run as the fused head kernels (csrc/head.hip); subclasses whose
     # last Linear is not a plain one opt out.
     _fuse_head = True
+
+    # ---- dropout state (see DropoutState / F.dropout_keep_mask)
+    @property
+    def dropout_seed(self) -> int:
+        return self._dropout.seed
+
+    @dropout_seed.setter
+    def dropout_seed(self, seed: int):
+        self._dropout.seed = int(seed)
+
+    @property
+    def dropout_step(self) -> int:
+        """Optimizer steps taken: the mask's `step` counter word."""
+        return self._dropout.step
+
+    @dropout_step.setter
+    def dropout_step(self, step: int):
+        self._dropout.step = int(step)
+
+    def set_sample_rows(self, mubatch_id: int, first: int, stride: int = 1):
+        """Row i of µbatch `mubatch_id` is sample first + i·stride of
+        the unsharded dataset order (the Worker sets this before each
+        Forward; default (0, 1) for hand-driven models)."""
+        self._dropout.rows[mubatch_id] = (int(first), int(stride))
+
+    def has_dropout(self) -> bool:
+        """Whether any layer was built with dropout > 0."""
+        return self._has_dropout
 
     def _head_pair(self):
         """(last Linear, SoftmaxXent head) when the chain ends in that
@@ -581,6 +718,12 @@ class Sequential(Module):
             plan.append((i, in_chain))
             if not in_chain:
                 break
+        # one dz scale per launch: the chain only when every planned
+        # layer has the same drop probability (all 0: today's kernel);
+        # a mix takes the per-layer path
+        if self._has_dropout and \
+                len({self.layers[i].dz_scale() for i, _ in plan}) > 1:
+            return None
         return plan or None
 
     def _wgrad_of(self, layer, dz, x):
@@ -611,9 +754,14 @@ class Sequential(Module):
             target = target.to(s.dtype)
         if not target.is_contiguous():
             target = target.contiguous()
-        res = F.bwd_chain(
-            s, target, lin.weight.compute_t(), head.global_batch_size, hs,
-            [l.weight.compute_t() for l, (_, dg) in zip(chain, plan) if dg])
+        w_ts = [l.weight.compute_t() for l, (_, dg) in zip(chain, plan) if dg]
+        if self._has_dropout:
+            res = F.bwd_chain(s, target, lin.weight.compute_t(),
+                              head.global_batch_size, hs, w_ts,
+                              dz_scale=chain[0].dz_scale())
+        else:
+            res = F.bwd_chain(s, target, lin.weight.compute_t(),
+                              head.global_batch_size, hs, w_ts)
         if res is None:
             return False, None
         dz_head, dzs, dx = res
@@ -793,10 +941,15 @@ class MLP(Sequential):
     very last Linear of the last stage (layers.py:251-260), and the last
     stage appends the fused loss head (reference: Softmax+MSELoss,
     layers.py:261-263; default here: softmax-cross-entropy).
+
+    dropout=p puts inverted dropout on every ReLU Linear (never on the
+    head Linear) with layer_index = the Linear's index in the full
+    `sizes` list, and dropout_seed seeds the mask: every stage of every
+    partition then draws the serial model's bits.
     """
 
     def __init__(self, sizes, stage_idx=0, n_stages=1, global_batch_size=1,
-                 loss="xent"):
+                 loss="xent", dropout=0.0, dropout_seed=0):
         assert len(sizes) % n_stages == 0, (
             f"len(sizes)={len(sizes)} must divide into {n_stages} stages"
         )
@@ -807,11 +960,19 @@ class MLP(Sequential):
         layers = []
         for i, (a, b) in enumerate(zip(bounds[:-1], bounds[1:])):
             last_linear = is_last and i == len(bounds) - 2
-            layers.append(Linear(a, b, activation=None if last_linear else "relu"))
+            # dropout on every ReLU Linear, never on the head Linear;
+            # layer_index is global so stage slicing keeps the mask
+            if last_linear:
+                layers.append(Linear(a, b, activation=None,
+                                     layer_index=lo + i))
+            else:
+                layers.append(Linear(a, b, activation="relu",
+                                     dropout=dropout, layer_index=lo + i))
         if is_last:
             head = {"xent": SoftmaxXent, "mse": SoftmaxMSE}[loss](global_batch_size)
             layers.append(head)
         super().__init__(layers)
+        self.dropout_seed = dropout_seed
         self.stage_idx, self.n_stages = stage_idx, n_stages
         self._skip_input_grad = stage_idx == 0
         self.in_dim = bounds[0]

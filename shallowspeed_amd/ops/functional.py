@@ -18,6 +18,8 @@ Differences from the reference, by design:
     (functional.py:30-35).
 """
 
+import functools
+
 import torch
 
 from ._ext import load_ext
@@ -273,13 +275,163 @@ def relu_fwd(x):
     return torch.clamp(x, min=0)
 
 
-def relu_bwd(dy, y):
+def relu_bwd(dy, y, scale=1.0):
     """dx = dy ⊙ 1[y>0] from the stashed ReLU OUTPUT (for relu,
     out>0 ⟺ in>0, so stashing the output replaces the reference's
-    bitmask stash at layers.py:70)."""
+    bitmask stash at layers.py:70).
+
+    scale != 1: the backward of ReLU + inverted dropout.  The stashed
+    output y = relu(z)·m/keep already is the mask (y>0 ⟺ z>0 ∧ m=1), so
+    dz = dy·scale where y>0 (rounded once, on GPU to bf16), +0 elsewhere
+    — NaN and −0.0 in y mask to +0, as without scale."""
+    if float(scale) == 1.0:
+        if _is_gpu(dy):
+            return _ext_for(dy).relu_bwd(dy, y)
+        return dy * (y > 0).to(dy.dtype)
     if _is_gpu(dy):
-        return _ext_for(dy).relu_bwd(dy, y)
-    return dy * (y > 0).to(dy.dtype)
+        return _ext_for(dy).relu_bwd_scaled(dy, y, float(scale))
+    return torch.where(y > 0, dy * float(scale), torch.zeros_like(dy))
+
+
+# ---------------------------------------------------------------- dropout
+#
+# One mask definition for every path (csrc/dropout_dev.h on the GPU, the
+# numpy code below on the CPU).  Element (sample, col) of layer `layer`
+# at optimizer step `step` under a 64-bit `seed`:
+#
+#   words = Philox4x32-10(counter = (sample, col >> 2, layer, step),
+#                         key     = (seed & 0xffffffff, seed >> 32))
+#   keep  = words[col & 3] < thr,   thr = min(2^32 − 1, round((1−p)·2^32))
+#   y     = keep ? y·float32(1/(1−p)) : +0       (f32, then ONE rounding)
+#
+# `sample` is the row's index in the UNSHARDED dataset order and `layer`
+# the Linear's index in the full `sizes` list, so the bits do not depend
+# on how DP, PP or micro-batching cut the batch.
+
+_PHILOX_M0, _PHILOX_M1 = 0xD2511F53, 0xCD9E8D57
+_PHILOX_W0, _PHILOX_W1 = 0x9E3779B9, 0xBB67AE85
+_U32 = 0xFFFFFFFF
+
+
+def philox4x32_10(counter, key):
+    """Philox4x32-10 on numpy uint64 arrays holding 32-bit values:
+    counter = four arrays (broadcastable), key = two ints.  Returns the
+    four output words as uint64 arrays (< 2^32)."""
+    import numpy as np
+
+    c0, c1, c2, c3 = np.broadcast_arrays(
+        *[np.asarray(c, dtype=np.uint64) for c in counter])
+    k0, k1 = int(key[0]) & _U32, int(key[1]) & _U32
+    m32 = np.uint64(_U32)
+    s32 = np.uint64(32)
+    for _ in range(10):
+        p0 = np.uint64(_PHILOX_M0) * c0  # 32 x 32 bits: fits 64
+        p1 = np.uint64(_PHILOX_M1) * c2
+        c0, c1, c2, c3 = ((p1 >> s32) ^ c1 ^ np.uint64(k0), p1 & m32,
+                          (p0 >> s32) ^ c3 ^ np.uint64(k1), p0 & m32)
+        k0 = (k0 + _PHILOX_W0) & _U32
+        k1 = (k1 + _PHILOX_W1) & _U32
+    return c0, c1, c2, c3
+
+
+@functools.lru_cache(maxsize=64)
+def dropout_params(p):
+    """(thr, scale) of drop probability p: keep when word < thr;
+    scale = float32(1/(1−p)) as a Python float.  Cached: the training
+    hot path asks for it per layer and step."""
+    import numpy as np
+
+    p = float(p)
+    if not 0.0 <= p < 1.0:
+        raise ValueError(f"dropout p must be in [0, 1), got {p}")
+    thr = min(_U32, int(np.floor((1.0 - p) * 4294967296.0 + 0.5)))
+    return thr, float(np.float32(1.0 / (1.0 - p)))
+
+
+def _seed_words(seed):
+    seed = int(seed)
+    assert 0 <= seed < 1 << 64, "dropout seed is 64 bits"
+    return seed & _U32, seed >> 32
+
+
+def dropout_keep_mask(seed, step, layer, sample_ids, ncols, p):
+    """Keep mask (bool, len(sample_ids) x ncols) of the dropout
+    definition above.  sample_ids: 1-D integer tensor (or sequence) of
+    unsharded sample indices, each < 2^32.  CPU: vectorised integer
+    numpy; a CUDA sample_ids tensor runs the small HIP kernel
+    (csrc/elementwise.hip) and returns a CUDA mask — same bits."""
+    import numpy as np
+
+    thr, _ = dropout_params(p)
+    k0, k1 = _seed_words(seed)
+    step, layer, ncols = int(step), int(layer), int(ncols)
+    assert 0 <= step <= _U32 and 0 <= layer <= _U32 and ncols >= 0
+    if not torch.is_tensor(sample_ids):
+        sample_ids = torch.as_tensor(list(sample_ids), dtype=torch.int64)
+    sample_ids = sample_ids.to(torch.int64).reshape(-1)
+    if sample_ids.numel():
+        assert int(sample_ids.min()) >= 0 and \
+            int(sample_ids.max()) <= _U32, "sample id must be < 2^32"
+    if _is_gpu(sample_ids):
+        return _ext_for(sample_ids).dropout_keep_mask(
+            sample_ids.contiguous(), ncols, k0, k1, step, layer, thr)
+    ngroups = (ncols + 3) // 4
+    s = sample_ids.numpy().astype(np.uint64)[:, None]
+    g = np.arange(ngroups, dtype=np.uint64)[None, :]
+    words = philox4x32_10((s, g, np.uint64(layer), np.uint64(step)),
+                          (k0, k1))
+    # (rows, groups, 4) -> (rows, 4 * groups): word col & 3 of group col >> 2
+    w = np.stack(words, axis=-1).reshape(s.shape[0], ngroups * 4)[:, :ncols]
+    return torch.from_numpy(w < np.uint64(thr))
+
+
+def _sample_ids(rows, row_first, row_stride, device):
+    assert row_first + max(rows - 1, 0) * row_stride <= _U32, \
+        "sample id must be < 2^32"
+    return row_first + row_stride * torch.arange(rows, dtype=torch.int64,
+                                                 device=device)
+
+
+def dropout_fwd_(y, seed, step, layer, row_first, row_stride, p):
+    """In-place inverted dropout of a finished post-ReLU activation y
+    (rows x cols); row i is sample row_first + i·row_stride.  The GPU
+    kernel (dropout_fwd_kernel: 16-B accesses, one Philox call per four
+    columns) serves the forward GEMM tiers without the fused epilogue
+    (glds, 256-tile, fp8).  Same mask as the fused path; a kept bf16
+    value is rounded a second time here, so it may differ from the
+    fused epilogue's by one bf16 ulp."""
+    thr, scale = dropout_params(p)
+    if _is_gpu(y):
+        k0, k1 = _seed_words(seed)
+        _ext_for(y).dropout_fwd_(y, k0, k1, int(step), int(layer),
+                                 int(row_first), int(row_stride), thr, scale)
+        return y
+    keep = dropout_keep_mask(
+        seed, step, layer,
+        _sample_ids(y.shape[0], row_first, row_stride, y.device),
+        y.shape[1], p)
+    y.copy_(torch.where(keep, y * scale, torch.zeros_like(y)))
+    return y
+
+
+def linear_fwd_dropout(x, w, b, seed, step, layer, row_first, row_stride, p,
+                       fused=True):
+    """y = dropout(relu(x @ W^T + b)), the training forward of a ReLU
+    Linear with drop probability p.
+
+    GPU: the mask rides in the epilogue of gemm_nt_kernel while the f32
+    accumulator is still in registers (one rounding to bf16); shapes
+    that dispatch to a tier without that epilogue (glds, 256-tile) run
+    the plain GEMM and then dropout_fwd_.  fused=False takes that
+    two-launch path at any shape (the measured alternative)."""
+    if _is_gpu(x):
+        thr, scale = dropout_params(p)
+        k0, k1 = _seed_words(seed)
+        return _ext_for(x).gemm_nt_dropout(
+            x, w, b, k0, k1, int(step), int(layer), int(row_first),
+            int(row_stride), thr, scale, bool(fused))
+    y = linear_fwd(x, w, b, relu=True)
+    return dropout_fwd_(y, seed, step, layer, row_first, row_stride, p)
 
 
 # ---------------------------------------------------------------- softmax
@@ -379,7 +531,7 @@ def head_bwd_fused(probs, target, x, w_t, global_batch, grad_w=None,
 
 
 def bwd_chain(probs, target, w_head_t, global_batch, hs, w_ts, rows=0,
-              waves=0, w_lds=0):
+              waves=0, w_lds=0, dz_scale=1.0):
     """Head backward plus the ReLU-layer data gradients below it in one
     kernel (GPU only, csrc/bwd_chain.hip).
 
@@ -395,13 +547,25 @@ def bwd_chain(probs, target, w_head_t, global_batch, hs, w_ts, rows=0,
     head_bwd_fused -> relu_bwd -> linear_dgrad -> ..., or None, with
     nothing launched, when the inputs are outside the kernel's contract
     (the caller takes the per-layer path).  rows / waves / w_lds select
-    the measured arms; 0 is the shipped choice."""
+    the measured arms; 0 is the shipped choice.
+
+    dz_scale != 1 (layers under inverted dropout, all with one p): every
+    kept dz_l element is bf16(dh · dz_scale), bit-identical to
+    relu_bwd(dh, h_l, scale=dz_scale).  One scale per launch; built for
+    the shipped arm only, so another arm returns None.  dz_scale == 1
+    runs the unscaled kernel."""
     if not _is_gpu(probs):
         return None
-    out = _ext_for(probs).bwd_chain(probs, target, w_head_t,
-                                    float(global_batch), list(hs),
-                                    list(w_ts), int(rows), int(waves),
-                                    int(w_lds))
+    if dz_scale == 1.0:
+        out = _ext_for(probs).bwd_chain(probs, target, w_head_t,
+                                        float(global_batch), list(hs),
+                                        list(w_ts), int(rows), int(waves),
+                                        int(w_lds))
+    else:
+        out = _ext_for(probs).bwd_chain(probs, target, w_head_t,
+                                        float(global_batch), list(hs),
+                                        list(w_ts), int(rows), int(waves),
+                                        int(w_lds), float(dz_scale))
     if not out:
         return None
     n = len(hs)

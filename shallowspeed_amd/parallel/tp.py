@@ -174,8 +174,13 @@ class TPMLP(Sequential):
     _fuse_head = False  # the TP head keeps the unfused chain
 
     def __init__(self, sizes, tp_group, tp_rank, tp_world,
-                 global_batch_size, loss="xent"):
+                 global_batch_size, loss="xent", dropout=0.0):
         from ..models.layers import SoftmaxMSE, SoftmaxXent
+
+        if dropout:
+            raise ValueError(
+                "TPMLP does not support dropout: the mask is keyed on "
+                "unsharded columns, which the TP layers do not track")
 
         layers = tp_mlp_layers(sizes, tp_group, tp_rank, tp_world)
         head = {"xent": SoftmaxXent, "mse": SoftmaxMSE}[loss](

@@ -70,6 +70,10 @@ class Worker:
         self.instruction_times = {}  # class name -> seconds (observability)
         self.comm_stats = {}         # p2p overlap counters (debug/timing)
         self._timing = False
+        # dropout anywhere in the model: sample rows are set per Forward
+        # and graph replay is off (see execute_graphed)
+        self._has_dropout = bool(
+            getattr(model, "has_dropout", lambda: False)())
 
         # training metrics (loss / accuracy / non-finite rows, counted
         # on device by the loss head).  None = SS_TRAIN_METRICS (default
@@ -93,6 +97,10 @@ class Worker:
             BackwardGradAcc: self._backward_acc,
             BackwardGradAllReduce: self._backward_and_reduce,
         }
+        if self._has_dropout:
+            # only a model with dropout pays for the two extra steps
+            self._DISPATCH[Forward] = self._forward_dropout
+            self._DISPATCH[OptimizerStep] = self._optimizer_step_dropout
 
     # ------------------------------------------------------------ metrics
     def set_metrics(self, on: bool):
@@ -335,7 +343,13 @@ class Worker:
     # staged into persistent buffers OUTSIDE the graph, and the
     # captured Load instructions read from the staging buffers.
     def execute_graphed(self, schedule, batch_id: int):
+        """Replay the step as a captured graph where that is possible.
+        A model with dropout in training mode runs eager: the mask's
+        step counter and sample rows are kernel ARGUMENTS, which a
+        replay would freeze at their captured values."""
         if self.device.type != "cuda" or self.topo.world > 1:
+            return self.execute(schedule, batch_id)
+        if self._has_dropout and self.model._training:
             return self.execute(schedule, batch_id)
         ds = self.dataset
         lb = ds.local_batch_size
@@ -514,6 +528,31 @@ class Worker:
     def _send_input_grad(self, cmd):
         self._isend("gout", cmd.buffer_idx,
                     self._gout_bufs[cmd.buffer_idx], self.topo.prev_rank)
+
+    def _set_sample_rows(self, mubatch_id):
+        """Tell the model which samples the µbatch's rows are (the
+        dropout mask is keyed on the sample, not on the launch).  The
+        strided DP shard puts local row j of rank r at j·dp + r of the
+        unsharded order, so row i of this µbatch is sample
+        (batch_id·local_batch + mubatch_id·mubatch + i)·dp + dp_rank —
+        computable on every pipeline stage."""
+        ds = self.dataset
+        if ds is None or not hasattr(ds, "local_batch_size"):
+            return
+        local = (self._batch_id * ds.local_batch_size
+                 + mubatch_id * ds.mubatch_size)
+        self.model.set_sample_rows(
+            mubatch_id, local * self.topo.dp + self.topo.dp_rank,
+            self.topo.dp)
+
+    def _forward_dropout(self, cmd):
+        self._set_sample_rows(cmd.mubatch_id)
+        self._forward(cmd)
+
+    def _optimizer_step_dropout(self, cmd):
+        self._optimizer_step(cmd)
+        # the mask's step counter: optimizer steps taken
+        self.model.dropout_step += 1
 
     def _forward(self, cmd):
         x = self._in_views.get(cmd.in_buffer)

@@ -110,6 +110,13 @@ def main():
                     help="MX-fp8 training forward on qualifying Linears "
                          "(O%%256,I%%256,µbatch%%256); backward stays bf16, "
                          "masters f32")
+    ap.add_argument("--dropout", type=float, default=0.0, metavar="P",
+                    help="inverted dropout with drop probability P on "
+                         "every ReLU layer (training only; the mask is "
+                         "keyed on the sample, so any --dp/--pp/--mubatches "
+                         "split draws the serial model's bits)")
+    ap.add_argument("--dropout-seed", type=int, default=0, metavar="N",
+                    help="64-bit seed of the dropout mask")
     ap.add_argument("--layer-sizes", type=parse_sizes,
                     default=[784, 128, 127, 126, 125, 124, 123, 10],
                     help="comma-separated boundaries (reference train.py:98)")
@@ -138,6 +145,12 @@ def main():
                     help="exit with status 3 after an epoch whose training "
                          "metrics saw a row with NaN/Inf probabilities")
     args = ap.parse_args()
+    if not 0.0 <= args.dropout < 1.0:
+        ap.error("--dropout must be in [0, 1)")
+    if args.dropout > 0 and args.tp > 1:
+        ap.error("--dropout is not supported with --tp > 1")
+    if not 0 <= args.dropout_seed < 1 << 64:
+        ap.error("--dropout-seed must fit 64 bits")
 
     assert args.global_batch % (args.dp * args.mubatches) == 0, \
         "--global-batch must divide by dp*mubatches"
@@ -162,7 +175,8 @@ def main():
     else:
         model = MLP(args.layer_sizes, stage_idx=topo.stage_id,
                     n_stages=args.pp,
-                    global_batch_size=args.global_batch, loss=args.loss)
+                    global_batch_size=args.global_batch, loss=args.loss,
+                    dropout=args.dropout, dropout_seed=args.dropout_seed)
     model.materialize_device(device)
     clip_kw = dict(clip_norm=args.clip_grad, flat_grad=model._flat_grad)
     if args.optimizer == "adamw":
@@ -216,7 +230,9 @@ def main():
 
     rprint(f"world={topo.world} dp={args.dp} pp={args.pp} "
            f"schedule={args.schedule} device={device} "
-           f"layers={args.layer_sizes} loss={args.loss}")
+           f"layers={args.layer_sizes} loss={args.loss}"
+           + (f" dropout={args.dropout} dropout_seed={args.dropout_seed}"
+              if args.dropout > 0 else ""))
 
     def lr_at(epoch):
         """Linear warmup then const/cosine decay (to 10% of peak)."""
