@@ -55,6 +55,19 @@ void check_table(const torch::Tensor& t, int64_t cols, const char* what) {
                 what);
 }
 
+// Output of an elementwise op: a fresh tensor like `like`, or the
+// caller's `out` (bf16, contiguous, same element count; may be a view
+// into a larger buffer, which is how the tests watch the elements behind
+// the written range).
+torch::Tensor out_like(const torch::Tensor& like,
+                       const std::optional<torch::Tensor>& out) {
+    if (!out.has_value()) return torch::empty_like(like);
+    check_bf16(*out, "out");
+    TORCH_CHECK(out->numel() == like.numel(), "out must hold ",
+                like.numel(), " elements, has ", out->numel());
+    return *out;
+}
+
 torch::Tensor gemm_nt(torch::Tensor a, torch::Tensor b, torch::Tensor bias,
                       torch::Tensor mask, bool relu) {
     check_bf16(a, "a");
@@ -301,29 +314,31 @@ torch::Tensor colsum(torch::Tensor dy, torch::Tensor mask) {
     return gb;
 }
 
-torch::Tensor relu_fwd(torch::Tensor x) {
+torch::Tensor relu_fwd(torch::Tensor x, std::optional<torch::Tensor> out) {
     check_bf16(x, "x");
-    auto y = torch::empty_like(x);
+    auto y = out_like(x, out);
     ss_relu_fwd(x.data_ptr(), y.data_ptr(), x.numel(), cur_stream());
     return y;
 }
 
-torch::Tensor relu_bwd(torch::Tensor dy, torch::Tensor y) {
+torch::Tensor relu_bwd(torch::Tensor dy, torch::Tensor y,
+                       std::optional<torch::Tensor> out) {
     check_bf16(dy, "dy");
     check_bf16(y, "y");
     TORCH_CHECK(dy.sizes() == y.sizes(), "shape mismatch");
-    auto dx = torch::empty_like(dy);
+    auto dx = out_like(dy, out);
     ss_relu_bwd(dy.data_ptr(), y.data_ptr(), dx.data_ptr(), dy.numel(),
                 cur_stream());
     return dx;
 }
 
 torch::Tensor relu_bwd_scaled(torch::Tensor dy, torch::Tensor y,
-                              double scale) {
+                              double scale,
+                              std::optional<torch::Tensor> out) {
     check_bf16(dy, "dy");
     check_bf16(y, "y");
     TORCH_CHECK(dy.sizes() == y.sizes(), "shape mismatch");
-    auto dx = torch::empty_like(dy);
+    auto dx = out_like(dy, out);
     ss_relu_bwd_scaled(dy.data_ptr(), y.data_ptr(), dx.data_ptr(), dy.numel(),
                        (float)scale, cur_stream());
     return dx;
@@ -360,11 +375,12 @@ torch::Tensor head_mse_bwd(torch::Tensor s, torch::Tensor t,
 }
 
 torch::Tensor head_xent_bwd(torch::Tensor s, torch::Tensor t,
-                            double global_batch) {
+                            double global_batch,
+                            std::optional<torch::Tensor> out) {
     check_bf16(s, "probs");
     check_bf16(t, "target");
     TORCH_CHECK(s.sizes() == t.sizes(), "shape mismatch");
-    auto dz = torch::empty_like(s);
+    auto dz = out_like(s, out);
     ss_head_xent_bwd(s.data_ptr(), t.data_ptr(), dz.data_ptr(), s.numel(),
                      (float)(1.0 / global_batch), cur_stream());
     return dz;
@@ -600,17 +616,19 @@ void ln_bwd_dparam(torch::Tensor dy, torch::Tensor x, torch::Tensor mean,
                      dy.size(0), dy.size(1), cur_stream());
 }
 
-torch::Tensor gelu_fwd(torch::Tensor z) {
+torch::Tensor gelu_fwd(torch::Tensor z, std::optional<torch::Tensor> out) {
     check_bf16(z, "z");
-    auto y = torch::empty_like(z);
+    auto y = out_like(z, out);
     ss_gelu_fwd(z.data_ptr(), y.data_ptr(), z.numel(), cur_stream());
     return y;
 }
 
-torch::Tensor gelu_bwd(torch::Tensor dy, torch::Tensor z) {
+torch::Tensor gelu_bwd(torch::Tensor dy, torch::Tensor z,
+                       std::optional<torch::Tensor> out) {
     check_bf16(dy, "dy");
     check_bf16(z, "z");
-    auto dz = torch::empty_like(dy);
+    TORCH_CHECK(dy.sizes() == z.sizes(), "shape mismatch");
+    auto dz = out_like(dy, out);
     ss_gelu_bwd(dy.data_ptr(), z.data_ptr(), dz.data_ptr(), dy.numel(),
                 cur_stream());
     return dz;
@@ -713,10 +731,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("colsum", &colsum, "standalone column sum (bias grad)");
     m.def("wgrad_tn_multi", &wgrad_tn_multi,
           "chunked (deferred-µbatch) wgrad: one launch, many (dy,x) pairs");
-    m.def("relu_fwd", &relu_fwd);
-    m.def("relu_bwd", &relu_bwd);
+    m.def("relu_fwd", &relu_fwd, py::arg("x"), py::arg("out") = py::none());
+    m.def("relu_bwd", &relu_bwd, py::arg("dy"), py::arg("y"),
+          py::arg("out") = py::none());
     m.def("relu_bwd_scaled", &relu_bwd_scaled,
-          "dz = bf16(dy * scale) where y > 0, else +0");
+          "dz = bf16(dy * scale) where y > 0, else +0", py::arg("dy"),
+          py::arg("y"), py::arg("scale"), py::arg("out") = py::none());
     m.def("gemm_nt_dropout", &gemm_nt_dropout,
           "C = dropout(relu(A @ B^T + bias)), mask in the GEMM epilogue",
           py::arg("a"), py::arg("b"), py::arg("bias"), py::arg("key0"),
@@ -730,7 +750,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("softmax_fwd", &softmax_fwd);
     m.def("softmax_bwd", &softmax_bwd);
     m.def("head_mse_bwd", &head_mse_bwd);
-    m.def("head_xent_bwd", &head_xent_bwd);
+    m.def("head_xent_bwd", &head_xent_bwd, py::arg("probs"),
+          py::arg("target"), py::arg("global_batch"),
+          py::arg("out") = py::none());
     m.def("head_fwd_fused", &head_fwd_fused,
           "fused head forward: softmax(bf16(x @ w^T + b))", py::arg("x"),
           py::arg("w"), py::arg("b"), py::arg("rows_per_block") = 0);
@@ -761,7 +783,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("ln_fwd", &ln_fwd);
     m.def("ln_bwd_dx", &ln_bwd_dx);
     m.def("ln_bwd_dparam", &ln_bwd_dparam);
-    m.def("gelu_fwd", &gelu_fwd);
-    m.def("gelu_bwd", &gelu_bwd);
+    m.def("gelu_fwd", &gelu_fwd, py::arg("z"), py::arg("out") = py::none());
+    m.def("gelu_bwd", &gelu_bwd, py::arg("dy"), py::arg("z"),
+          py::arg("out") = py::none());
     m.def("row_argmax", &row_argmax);
 }

@@ -170,7 +170,7 @@ __global__ __launch_bounds__(256) void softmax_fwd_kernel(
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= B) return;
     const __bf16* xr = x + (long)row * C;
-    float m = -1e30f;
+    float m = -INFINITY;  // any finite start would cap rows below it
     for (int c = lane; c < C; c += 64) m = fmaxf(m, bf2f(xr[c]));
     m = wave_max(m);
     float sum = 0.f;
@@ -256,7 +256,10 @@ __global__ __launch_bounds__(256) void row_argmax_kernel(
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= B) return;
     const __bf16* xr = x + (long)row * C;
-    float best = -1e30f;
+    // -Inf, not a finite floor: a row that lies wholly below the floor
+    // would return 0.  A lane with no column keeps (-Inf, 0), which can
+    // only win a row that is all -Inf, where 0 is the answer.
+    float best = -INFINITY;
     int bi = 0;
     for (int c = lane; c < C; c += 64) {
         const float v = bf2f(xr[c]);

@@ -3,6 +3,8 @@
 //
 // LayerNorm: wave-per-row, f32 statistics, bf16 I/O.
 //   fwd: y = (x - µ) * rstd * γ + β ; saves µ, rstd per row.
+//       Two-pass statistics: µ = Σx / C, then var = Σ(x - µ)² / C;
+//       rows of up to 1024 elements are held in registers between passes.
 //   bwd (input grad): dx = rstd * (g - mean(g) - x̂ * mean(g * x̂)),
 //       g = dy * γ, x̂ = (x - µ) * rstd  — wave-per-row.
 //   bwd (param grads): dγ[c] += Σ_rows dy * x̂ ; dβ[c] += Σ_rows dy —
@@ -15,6 +17,16 @@
 
 // --------------------------------------------------------------- layernorm
 
+// Statistics in two passes, as the CPU path defines them: mu = sum x / C,
+// then var = sum (x - mu)^2 / C, non-negative by construction.  (A
+// one-pass E[x^2] - mu^2 cancels to an absolute error of C ulps of mu^2:
+// on a constant or large-mean row that is as large as var + eps, or
+// negative, and rsqrt returns NaN.)
+// R > 0: the row fits R elements per lane (C <= 64 R) and is read ONCE
+// into registers for all three passes; R = 0: any C, each pass re-reads
+// the row (in cache).  Lane-strided in both, so a lane adds the same
+// values in the same order either way.
+template <int R>
 __global__ __launch_bounds__(256) void ln_fwd_kernel(
     const __bf16* __restrict__ x, const __bf16* __restrict__ gamma,
     const __bf16* __restrict__ beta, __bf16* __restrict__ y,
@@ -24,25 +36,51 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= B) return;
     const __bf16* xr = x + (long)row * C;
+    __bf16* yr = y + (long)row * C;
+    float v[R > 0 ? R : 1];
     float s = 0.f, s2 = 0.f;
-    for (int c = lane; c < C; c += 64) {
-        const float v = bf2f(xr[c]);
-        s += v;
-        s2 += v * v;
+    if constexpr (R > 0) {
+#pragma unroll
+        for (int k = 0; k < R; ++k) {
+            const int c = lane + 64 * k;
+            v[k] = c < C ? bf2f(xr[c]) : 0.f;
+            s += v[k];
+        }
+    } else {
+        for (int c = lane; c < C; c += 64) s += bf2f(xr[c]);
     }
-    s = wave_sum(s);
-    s2 = wave_sum(s2);
-    const float mu = s / C;
-    const float var = s2 / C - mu * mu;
+    const float mu = wave_sum(s) / C;
+    if constexpr (R > 0) {
+#pragma unroll
+        for (int k = 0; k < R; ++k) {
+            const float d = lane + 64 * k < C ? v[k] - mu : 0.f;
+            s2 += d * d;
+        }
+    } else {
+        for (int c = lane; c < C; c += 64) {
+            const float d = bf2f(xr[c]) - mu;
+            s2 += d * d;
+        }
+    }
+    const float var = wave_sum(s2) / C;
     const float rs = rsqrtf(var + eps);
     if (lane == 0) {
         mean[row] = mu;
         rstd[row] = rs;
     }
-    __bf16* yr = y + (long)row * C;
-    for (int c = lane; c < C; c += 64) {
-        const float xh = (bf2f(xr[c]) - mu) * rs;
-        yr[c] = f2bf(xh * bf2f(gamma[c]) + bf2f(beta[c]));
+    if constexpr (R > 0) {
+#pragma unroll
+        for (int k = 0; k < R; ++k) {
+            const int c = lane + 64 * k;
+            if (c < C)
+                yr[c] = f2bf((v[k] - mu) * rs * bf2f(gamma[c]) +
+                             bf2f(beta[c]));
+        }
+    } else {
+        for (int c = lane; c < C; c += 64) {
+            const float xh = (bf2f(xr[c]) - mu) * rs;
+            yr[c] = f2bf(xh * bf2f(gamma[c]) + bf2f(beta[c]));
+        }
     }
 }
 
@@ -148,10 +186,16 @@ __global__ __launch_bounds__(256) void gelu_bwd_kernel(
 void ss_ln_fwd(const void* x, const void* gamma, const void* beta, void* y,
                void* mean, void* rstd, int B, int C, float eps,
                hipStream_t st) {
-    hipLaunchKernelGGL(ln_fwd_kernel, dim3(cdiv(B, 4)), dim3(256), 0, st,
-                       (const __bf16*)x, (const __bf16*)gamma,
-                       (const __bf16*)beta, (__bf16*)y, (float*)mean,
-                       (float*)rstd, B, C, eps);
+    // rows of up to 256 / 1024 elements stay in 4 / 16 registers a lane
+    auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3(cdiv(B, 4)), dim3(256), 0, st,
+                           (const __bf16*)x, (const __bf16*)gamma,
+                           (const __bf16*)beta, (__bf16*)y, (float*)mean,
+                           (float*)rstd, B, C, eps);
+    };
+    if (C <= 256) launch(ln_fwd_kernel<4>);
+    else if (C <= 1024) launch(ln_fwd_kernel<16>);
+    else launch(ln_fwd_kernel<0>);
 }
 
 void ss_ln_bwd_dx(const void* dy, const void* x, const void* gamma,

@@ -272,7 +272,10 @@ def relu_fwd(x):
     the fused GEMM epilogue instead."""
     if _is_gpu(x):
         return _ext_for(x).relu_fwd(x)
-    return torch.clamp(x, min=0)
+    # x where x > 0, else +0: -0.0 gives +0 like the kernel (clamp keeps
+    # its sign); NaN stays NaN here, the kernel maps it to +0
+    # (docs/KERNELS.md)
+    return torch.where(x <= 0, torch.zeros_like(x), x)
 
 
 def relu_bwd(dy, y, scale=1.0):
@@ -287,7 +290,9 @@ def relu_bwd(dy, y, scale=1.0):
     if float(scale) == 1.0:
         if _is_gpu(dy):
             return _ext_for(dy).relu_bwd(dy, y)
-        return dy * (y > 0).to(dy.dtype)
+        # not dy * mask: that leaves -0 under a negative dy and NaN under
+        # an infinite one
+        return torch.where(y > 0, dy, torch.zeros_like(dy))
     if _is_gpu(dy):
         return _ext_for(dy).relu_bwd_scaled(dy, y, float(scale))
     return torch.where(y > 0, dy * float(scale), torch.zeros_like(dy))
