@@ -552,6 +552,60 @@ std::vector<torch::Tensor> bwd_chain(torch::Tensor probs, torch::Tensor target,
     return out;
 }
 
+// Forward chain (fwd_chain.hip): the 256-wide ReLU layers under the
+// head and the fused head in one launch.  ws[l] / bs[l], bottom layer
+// first; x is the input of layer 0 (256 wide, or any multiple of 8 when
+// the first layer streams it).  Returns [h_0, ..., h_{n-1}, probs], or
+// an EMPTY list, with nothing allocated or launched, when the inputs are
+// outside the kernel's contract: the caller then takes the per-layer
+// path.
+std::vector<torch::Tensor> fwd_chain(torch::Tensor x,
+                                     std::vector<torch::Tensor> ws,
+                                     std::vector<torch::Tensor> bs,
+                                     torch::Tensor w_head,
+                                     torch::Tensor b_head, int64_t rows,
+                                     int64_t waves, int64_t l1) {
+    auto plain = [](const torch::Tensor& t, int64_t dim) {
+        return t.is_cuda() && t.scalar_type() == torch::kBFloat16 &&
+               t.dim() == dim && t.is_contiguous() && t.numel() > 0 &&
+               ((uintptr_t)t.data_ptr() & 15) == 0;
+    };
+    constexpr int64_t H = 256;
+    const int64_t n = (int64_t)ws.size();
+    if (n < 1 || n > SS_FWD_CHAIN_MAX || (int64_t)bs.size() != n) return {};
+    if (!plain(x, 2) || !plain(w_head, 2) || !plain(b_head, 1)) return {};
+    const int64_t M = x.size(0), K0 = x.size(1), C = w_head.size(0);
+    if (M > INT_MAX / 1024 || K0 % 8 != 0 || C > 16 ||
+        w_head.size(1) != H || b_head.numel() != C)
+        return {};
+    if ((rows != 0 && rows != 32 && rows != 64) ||
+        (waves != 0 && waves != 4 && waves != 8) || l1 < 0 || l1 > 2 ||
+        (l1 == 1 && K0 != H))
+        return {};
+    const void* wp[SS_FWD_CHAIN_MAX] = {};
+    const void* bp[SS_FWD_CHAIN_MAX] = {};
+    void* hp[SS_FWD_CHAIN_MAX] = {};
+    for (int64_t l = 0; l < n; ++l) {
+        if (!plain(ws[l], 2) || !plain(bs[l], 1) || ws[l].size(0) != H ||
+            ws[l].size(1) != (l == 0 ? K0 : H) || bs[l].numel() != H)
+            return {};
+        wp[l] = ws[l].data_ptr();
+        bp[l] = bs[l].data_ptr();
+    }
+    std::vector<torch::Tensor> out;
+    for (int64_t l = 0; l < n; ++l) {
+        out.push_back(torch::empty({M, H}, x.options()));
+        hp[l] = out.back().data_ptr();
+    }
+    out.push_back(torch::empty({M, C}, x.options()));
+    if (!ss_fwd_chain(x.data_ptr(), wp, bp, hp, (int)n, w_head.data_ptr(),
+                      b_head.data_ptr(), out.back().data_ptr(), (int)M,
+                      (int)K0, (int)H, (int)C, (int)rows, (int)waves, (int)l1,
+                      cur_stream()))
+        return {};
+    return out;
+}
+
 // Adds the metric totals of (probs, target) into acc: loss_sum (kind
 // "xent" or "mse"), argmax matches, rows, non-finite rows.
 void head_metrics(torch::Tensor probs, torch::Tensor target,
@@ -769,6 +823,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           py::arg("global_batch"), py::arg("hs"), py::arg("w_ts"),
           py::arg("rows") = 0, py::arg("waves") = 0, py::arg("w_lds") = 0,
           py::arg("dz_scale") = 1.0);
+    m.def("fwd_chain", &fwd_chain,
+          "256-wide ReLU layers + fused head forward in one launch -> "
+          "[h_l..., probs], or [] outside the contract",
+          py::arg("x"), py::arg("ws"), py::arg("bs"), py::arg("w_head"),
+          py::arg("b_head"), py::arg("rows") = 0, py::arg("waves") = 0,
+          py::arg("l1") = 0);
     m.def("head_metrics", &head_metrics,
           "metric totals of (probs, target) into a slotted accumulator",
           py::arg("probs"), py::arg("target"), py::arg("acc"),

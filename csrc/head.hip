@@ -184,29 +184,8 @@ __global__ __launch_bounds__(WAVES * 64) void head_fwd_fused_kernel(
 
     // ---- epilogue in registers: lane (kch, lrow) holds rows
     // kch*4 + r of column lrow; the 16 lanes of one kch hold one row
-    const float bv = cvalid ? bf2f(bias[lrow]) : 0.f;
-#pragma unroll
-    for (int f = 0; f < FR; ++f) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            float v = acc[f][r];
-            v += bv;
-            v = bf2f(f2bf(v));  // the logit as the unfused path stores it
-            float m = cvalid ? fmaxf(-1e30f, v) : -1e30f;
-#pragma unroll
-            for (int off = 8; off > 0; off >>= 1)
-                m = fmaxf(m, __shfl_xor(m, off, 64));
-            const float e = cvalid ? __expf(v - m) : 0.f;
-            float s = e;
-#pragma unroll
-            for (int off = 8; off > 0; off >>= 1)
-                s += __shfl_xor(s, off, 64);
-            const float inv = 1.f / s;
-            const int row = row_base + f * 16 + kch * 4 + r;
-            if (cvalid && row < M)
-                probs[(long)row * C + lrow] = f2bf(e * inv);
-        }
-    }
+    // (head_dev.h: the forward chain kernel runs the same code)
+    HEAD_FWD_EPILOGUE(FR, acc, bias, probs, cvalid, lrow, kch, row_base, M, C)
 }
 
 // --------------------------------------------------------------- backward

@@ -1,7 +1,9 @@
-// Device code of the classifier-head backward that more than one kernel
-// runs: head_bwd_fused_kernel (head.hip) and bwd_chain_kernel
-// (bwd_chain.hip) both produce dz and dx of the head through these, so
-// the two cannot drift apart in their bits.
+// Device code of the classifier head that more than one kernel runs:
+// head_bwd_fused_kernel (head.hip) and bwd_chain_kernel (bwd_chain.hip)
+// both produce dz and dx of the head through these, and
+// head_fwd_fused_kernel and fwd_chain_kernel (fwd_chain.hip) both
+// produce probs through HEAD_FWD_EPILOGUE, so the pairs cannot drift
+// apart in their bits.
 //
 // The two larger pieces are statement macros, not functions: as
 // force-inlined functions they left head_bwd_fused_kernel with a
@@ -45,6 +47,35 @@ __device__ __forceinline__ __bf16 head_dz_elem(__bf16 pb, __bf16 tb,
         }                                                                    \
         *(bf16x8*)&wts[tid][0] = lo;                                         \
         *(bf16x8*)&wts[tid][8] = hi;                                         \
+    }
+
+// Register epilogue of the head forward, run by head_fwd_fused_kernel
+// (head.hip) and fwd_chain_kernel (fwd_chain.hip): acc[FR] are the
+// 16x16 logit fragments of rows row_base + f*16.. (lane (kch, lrow)
+// holds rows kch*4 + r of column lrow; the 16 lanes of one kch hold one
+// row).  Bias, the logit rounded to bf16 as the unfused path stores it,
+// row max, __expf, the xor tree over the row's 16 lanes and the scaled
+// store of probs[M][C]; cvalid = lrow < C.
+#define HEAD_FWD_EPILOGUE(FR, acc, bias, probs, cvalid, lrow, kch,          \
+                          row_base, M, C)                                    \
+    const float bv = cvalid ? bf2f(bias[lrow]) : 0.f;                        \
+    _Pragma("unroll") for (int f = 0; f < FR; ++f) {                         \
+        _Pragma("unroll") for (int r = 0; r < 4; ++r) {                      \
+            float v = acc[f][r];                                             \
+            v += bv;                                                         \
+            v = bf2f(f2bf(v)); /* the logit as the unfused path stores it */ \
+            float m = cvalid ? fmaxf(-1e30f, v) : -1e30f;                    \
+            _Pragma("unroll") for (int off = 8; off > 0; off >>= 1)          \
+                m = fmaxf(m, __shfl_xor(m, off, 64));                        \
+            const float e = cvalid ? __expf(v - m) : 0.f;                    \
+            float s = e;                                                     \
+            _Pragma("unroll") for (int off = 8; off > 0; off >>= 1)          \
+                s += __shfl_xor(s, off, 64);                                 \
+            const float inv = 1.f / s;                                       \
+            const int row = row_base + f * 16 + kch * 4 + r;                 \
+            if (cvalid && row < M)                                           \
+                probs[(long)row * C + lrow] = f2bf(e * inv);                 \
+        }                                                                    \
     }
 
 // Declares f32x4 `acc`: one 16x16 dx fragment of the head, rows rg*16..

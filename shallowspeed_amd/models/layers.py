@@ -612,11 +612,82 @@ class Sequential(Module):
             return lin, head
         return None
 
+    def _fwd_chain_plan(self):
+        """Which layers the forward chain kernel (F.fwd_chain) takes
+        together with the head: their indices, bottom first, or None
+        when the head or the layers under it do not qualify.
+
+        The chain is the fused head (Linear(256 -> C <= 16) +
+        SoftmaxXent) and the run of Linear(activation="relu") layers
+        with out_dims == 256 right below it, at most eight.  A layer is
+        in the chain when in_dims == 256, or, with F.fwd_chain_l1(),
+        when it ends the run and in_dims % 8 == 0.  No chain with
+        dropout or an fp8 forward on a layer it would take.  Looks at
+        the layer configuration only — no tensors, no device."""
+        pair = self._head_pair()
+        if pair is None or not F.fwd_chain_enabled() or not F.head_fused():
+            return None
+        lin = pair[0]
+        if lin.in_dims != self._CHAIN_WIDTH or lin.out_dims > 16 \
+                or lin.fp8_fwd:
+            return None
+        plan = []
+        for i in range(len(self.layers) - 3, -1, -1):
+            layer = self.layers[i]
+            if len(plan) == self._CHAIN_MAX_LAYERS \
+                    or type(layer) is not Linear \
+                    or layer.activation != "relu" \
+                    or layer.out_dims != self._CHAIN_WIDTH:
+                break
+            streamed = layer.in_dims != self._CHAIN_WIDTH
+            if streamed and not (F.fwd_chain_l1() and layer.in_dims >= 8
+                                 and layer.in_dims % 8 == 0):
+                break
+            if layer.dropout > 0.0 or layer.fp8_fwd:
+                return None
+            plan.append(i)
+            if streamed:
+                break
+        return plan[::-1] or None
+
+    def _forward_chain(self, plan, lin, head, x, mubatch_id):
+        """Forward of the planned ReLU layers and the head pair through
+        ONE F.fwd_chain launch, leaving the stashes the layers' own
+        forwards leave.  Returns probs, or None with no stash touched
+        when the tensors do not meet the kernel's contract."""
+        if not F.head_fused_ok(x, lin):
+            return None
+        chain = [self.layers[i] for i in plan]
+        res = F.fwd_chain(x, [l.weight.compute() for l in chain],
+                          [l.bias.compute() for l in chain],
+                          lin.weight.compute(), lin.bias.compute())
+        if res is None:
+            return None
+        hs, probs = res
+        for layer, h in zip(chain, hs):
+            layer._stash("x", mubatch_id, x)
+            layer._stash("y", mubatch_id, h)
+            x = h
+        lin._stash("x", mubatch_id, x)
+        head._stash("s", mubatch_id, probs)
+        return probs
+
     def forward(self, inputs, mubatch_id: int = 0):
         x = inputs
         pair = self._head_pair()
         n_plain = len(self.layers) - 2 if pair else len(self.layers)
-        for layer in self.layers[:n_plain]:
+        plan = self._fwd_chain_plan() if pair and inputs.is_cuda else None
+        if plan:
+            # layers below the chain run their own forward first
+            for layer in self.layers[:plan[0]]:
+                x = layer.forward(x, mubatch_id)
+            s = self._forward_chain(plan, pair[0], pair[1], x, mubatch_id)
+            if s is not None:
+                return s
+            first = plan[0]
+        else:
+            first = 0
+        for layer in self.layers[first:n_plain]:
             x = layer.forward(x, mubatch_id)
         if pair:
             lin, head = pair

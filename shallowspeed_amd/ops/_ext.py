@@ -82,6 +82,7 @@ def build_ext(verbose=True):
         os.path.join(src_dir, "elementwise.hip"),
         os.path.join(src_dir, "head.hip"),
         os.path.join(src_dir, "bwd_chain.hip"),
+        os.path.join(src_dir, "fwd_chain.hip"),
         os.path.join(src_dir, "norm.hip"),
         os.path.join(src_dir, "fused_mlp.hip"),
     ]

@@ -132,6 +132,44 @@ def bwd_chain_dz_last() -> bool:
     return _BWD_CHAIN_DZ_LAST
 
 
+_FWD_CHAIN = None
+
+
+def set_fwd_chain(flag: bool):
+    """Run the 256-wide ReLU layers under the fused head and the head
+    forward as the one kernel of csrc/fwd_chain.hip (see fwd_chain).
+    Every h_l and probs keeps its bits.  Default on; SS_FWD_CHAIN=0
+    (read once) turns it off."""
+    global _FWD_CHAIN
+    _FWD_CHAIN = bool(flag)
+
+
+def fwd_chain_enabled() -> bool:
+    global _FWD_CHAIN
+    if _FWD_CHAIN is None:
+        import os
+
+        _FWD_CHAIN = os.environ.get("SS_FWD_CHAIN", "1") != "0"
+    return _FWD_CHAIN
+
+
+_FWD_CHAIN_L1 = None
+
+
+def fwd_chain_l1() -> bool:
+    """Whether the forward chain also takes a lowest layer that is not
+    256 wide at its input (the flagship's 784-wide first layer),
+    streaming x through LDS.  Default on.  Off (SS_FWD_CHAIN_L1=0, read
+    once: the measured alternative), that layer stays a gemm_nt launch
+    and the chain starts from its stored output."""
+    global _FWD_CHAIN_L1
+    if _FWD_CHAIN_L1 is None:
+        import os
+
+        _FWD_CHAIN_L1 = os.environ.get("SS_FWD_CHAIN_L1", "1") != "0"
+    return _FWD_CHAIN_L1
+
+
 def _is_gpu(t: torch.Tensor) -> bool:
     return t.is_cuda
 
@@ -575,6 +613,31 @@ def bwd_chain(probs, target, w_head_t, global_batch, hs, w_ts, rows=0,
         return None
     n = len(hs)
     return out[0], out[1:1 + n], (out[1 + n] if len(w_ts) == n else None)
+
+
+def fwd_chain(x, ws, bs, w_head, b_head, rows=0, waves=0, l1=0):
+    """The ReLU layers under the fused head and the head forward in one
+    kernel (GPU only, csrc/fwd_chain.hip).
+
+    ws / bs: weights (256, in) and biases of the chain's layers, bottom
+    layer first; x: the input of the lowest one, (M, 256), or (M, any
+    multiple of 8) when that layer streams its input.
+
+      h_l = relu(h_{l-1} @ W_l^T + b_l) ; probs = softmax(h @ W_head^T + b)
+
+    Returns ([h_l, ...], probs), each bit-identical to linear_fwd(relu)
+    -> ... -> head_fwd_fused, or None, with nothing launched, when the
+    inputs are outside the kernel's contract (the caller takes the
+    per-layer path).  rows / waves select the measured arms, l1 how the
+    chain starts (1: from a stored 256-wide activation, 2: streaming
+    x); 0 is the shipped choice."""
+    if not _is_gpu(x):
+        return None
+    out = _ext_for(x).fwd_chain(x, list(ws), list(bs), w_head, b_head,
+                                int(rows), int(waves), int(l1))
+    if not out:
+        return None
+    return out[:-1], out[-1]
 
 
 def xent_loss(probs, target, global_batch, eps=1e-9):
