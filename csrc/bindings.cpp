@@ -405,6 +405,15 @@ void check_align16(const torch::Tensor& t, const char* name) {
                 " must be 16-byte aligned");
 }
 
+// Operand of the chain kernels: CUDA, bf16, `dim`-D, contiguous,
+// non-empty, 16-byte aligned.  The chain bindings refuse (return [])
+// where another binding would raise.
+bool plain(const torch::Tensor& t, int64_t dim) {
+    return t.is_cuda() && t.scalar_type() == torch::kBFloat16 &&
+           t.dim() == dim && t.is_contiguous() && t.numel() > 0 &&
+           aligned16(t.data_ptr());
+}
+
 // Fused classifier head (head.hip): probs = softmax(bf16(x @ w^T + b)).
 // rows_per_block: 0 = shipped choice, 32/64/128 = the measured arms.
 torch::Tensor head_fwd_fused(torch::Tensor x, torch::Tensor w,
@@ -498,15 +507,11 @@ std::vector<torch::Tensor> bwd_chain(torch::Tensor probs, torch::Tensor target,
                                      std::vector<torch::Tensor> w_ts,
                                      int64_t rows, int64_t waves,
                                      int64_t w_lds, double dz_scale) {
-    auto plain = [](const torch::Tensor& t) {
-        return t.is_cuda() && t.scalar_type() == torch::kBFloat16 &&
-               t.dim() == 2 && t.is_contiguous() &&
-               ((uintptr_t)t.data_ptr() & 15) == 0;
-    };
     const int64_t n = (int64_t)hs.size();
     const int64_t nw = (int64_t)w_ts.size();
     if (n < 1 || n > SS_BWD_CHAIN_MAX || (nw != n && nw != n - 1)) return {};
-    if (!plain(probs) || !plain(target) || !plain(w_head_t)) return {};
+    if (!plain(probs, 2) || !plain(target, 2) || !plain(w_head_t, 2))
+        return {};
     if (probs.sizes() != target.sizes()) return {};
     const int64_t M = probs.size(0), C = probs.size(1), H = w_head_t.size(0);
     if (M < 1 || M > INT_MAX / 512 || w_head_t.size(1) != C) return {};
@@ -514,11 +519,11 @@ std::vector<torch::Tensor> bwd_chain(torch::Tensor probs, torch::Tensor target,
     const void* wp[SS_BWD_CHAIN_MAX] = {};
     void* dp[SS_BWD_CHAIN_MAX] = {};
     for (int64_t l = 0; l < n; ++l) {
-        if (!plain(hs[l]) || hs[l].size(0) != M || hs[l].size(1) != H)
+        if (!plain(hs[l], 2) || hs[l].size(0) != M || hs[l].size(1) != H)
             return {};
         hp[l] = hs[l].data_ptr();
         if (l < nw) {
-            if (!plain(w_ts[l]) || w_ts[l].size(0) != H ||
+            if (!plain(w_ts[l], 2) || w_ts[l].size(0) != H ||
                 w_ts[l].size(1) != H)
                 return {};
             wp[l] = w_ts[l].data_ptr();
@@ -535,20 +540,12 @@ std::vector<torch::Tensor> bwd_chain(torch::Tensor probs, torch::Tensor target,
         out.push_back(torch::empty_like(hs[n - 1]));
         dx_p = out.back().data_ptr();
     }
-    // dz_scale 1.0 (no dropout) is today's unscaled kernel
-    const bool ok =
-        (float)dz_scale == 1.f
-            ? ss_bwd_chain(probs.data_ptr(), target.data_ptr(),
-                           w_head_t.data_ptr(), out[0].data_ptr(), hp, wp, dp,
-                           (int)n, dx_p, (int)M, (int)H, (int)C,
-                           (float)(1.0 / global_batch), (int)rows, (int)waves,
-                           (int)w_lds, cur_stream())
-            : ss_bwd_chain(probs.data_ptr(), target.data_ptr(),
-                           w_head_t.data_ptr(), out[0].data_ptr(), hp, wp, dp,
-                           (int)n, dx_p, (int)M, (int)H, (int)C,
-                           (float)(1.0 / global_batch), (int)rows, (int)waves,
-                           (int)w_lds, (float)dz_scale, cur_stream());
-    if (!ok) return {};
+    if (!ss_bwd_chain(probs.data_ptr(), target.data_ptr(),
+                      w_head_t.data_ptr(), out[0].data_ptr(), hp, wp, dp,
+                      (int)n, dx_p, (int)M, (int)H, (int)C,
+                      (float)(1.0 / global_batch), (int)rows, (int)waves,
+                      (int)w_lds, (float)dz_scale, cur_stream()))
+        return {};
     return out;
 }
 
@@ -565,11 +562,6 @@ std::vector<torch::Tensor> fwd_chain(torch::Tensor x,
                                      torch::Tensor w_head,
                                      torch::Tensor b_head, int64_t rows,
                                      int64_t waves, int64_t l1) {
-    auto plain = [](const torch::Tensor& t, int64_t dim) {
-        return t.is_cuda() && t.scalar_type() == torch::kBFloat16 &&
-               t.dim() == dim && t.is_contiguous() && t.numel() > 0 &&
-               ((uintptr_t)t.data_ptr() & 15) == 0;
-    };
     constexpr int64_t H = 256;
     const int64_t n = (int64_t)ws.size();
     if (n < 1 || n > SS_FWD_CHAIN_MAX || (int64_t)bs.size() != n) return {};

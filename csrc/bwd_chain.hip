@@ -33,14 +33,8 @@
 // C <= 16, 1..8 layers, M >= 1 (rows past M are guarded), every layer
 // but the last has its W^T, the last has it exactly when dx is wanted.
 
-#include "head_dev.h"
+#include "chain_dev.h"
 #include "launchers.h"
-
-// operands in the global address space: pointers that arrive inside the
-// by-value argument block would otherwise compile to FLAT loads, which
-// count on lgkmcnt with the LDS reads
-using gbf16 = __attribute__((address_space(1))) __bf16;
-using gbf16x8 = __attribute__((address_space(1))) bf16x8;
 
 // The layers of one launch, top first.  Passed BY VALUE (24 pointers of
 // kernel arguments): nothing to upload, nothing to keep alive, and
@@ -51,12 +45,11 @@ struct BwdChainLayers {
     void* dz[SS_BWD_CHAIN_MAX];        // masked gradient out
 };
 
-// R rows per tile, NW waves per block; wave w owns columns
-// [w*256/NW, +256/NW) of every dh tile.  Second launch bound = waves per
-// SIMD that two blocks on a CU need.  WLDS: W^T goes through LDS in
-// 32-wide K-chunks (register-staged, double-buffered, one barrier per
-// K-step, as gemm_nt_kernel stages B) instead of L2 -> registers; the
-// measured alternative (85 KB of LDS: one block per CU).
+// R rows per tile, NW waves per block (CHAIN_GEOMETRY).  Second launch
+// bound = waves per SIMD that two blocks on a CU need.  WLDS: W^T goes
+// through LDS in 32-wide K-chunks (register-staged, double-buffered, one
+// barrier per K-step, as gemm_nt_kernel stages B) instead of L2 ->
+// registers; the measured alternative (85 KB of LDS: one block per CU).
 // SCALED: the layers ran inverted dropout, so a kept dz element is
 // bf16(dh · dz_scale) with dz_scale = 1/keep, one value for the launch
 // (the stashed h already is the mask: h > 0 ⇔ z > 0 ∧ kept).  SA is that
@@ -73,19 +66,7 @@ void bwd_chain_kernel(
     __bf16* __restrict__ dx,             // [M][256] or null
     int M, int C, float inv_gb, int ntiles, SA... dz_scale) {
     static_assert(sizeof...(SA) == SCALED, "one dz_scale when SCALED");
-    constexpr int H = 256;
-    constexpr int NT = NW * 64;
-    constexpr int LDT = H + 8;          // padded tile row (bf16)
-    constexpr int PPR = H / 8;          // 16-B pieces per tile row
-    constexpr int NP = R * PPR / NT;    // pieces per thread
-    constexpr int FM = R / 16;          // 16-row fragments per tile
-    constexpr int WN = H / NW;          // columns per wave
-    constexpr int FN = WN / 16;
-    constexpr int NSTEP = H / 32;       // K-steps of a layer
-    // K-steps per B load group: two where the accumulators leave room
-    constexpr int U = (FM * FN <= 8 && NW == 4) ? 2 : 1;
-    constexpr int UNR = NW == 4 ? NSTEP / U : 1;  // K-loop unroll count
-    static_assert(R * PPR % NT == 0, "piece mapping");
+    CHAIN_GEOMETRY(R, NW);
     static_assert(NT >= H, "one thread per W_head^T row");
 
     __shared__ __attribute__((aligned(16))) ushort tile[R][LDT];
@@ -111,10 +92,7 @@ void bwd_chain_kernel(
         bf16x8 hm[NP];
         auto load_mask = [&](int l) {
             const gbf16* h = (const gbf16*)L.h[l];
-#pragma unroll
-            for (int i = 0; i < NP; ++i) {
-                const int q = tid + i * NT;
-                const int r = q / PPR, col = (q % PPR) * 8;
+            CHAIN_FOR_PIECES(i, r, col) {
                 hm[i] = zero8();
                 if (row0 + r < M)
                     hm[i] = *(const gbf16x8*)&h[(long)(row0 + r) * H + col];
@@ -152,10 +130,7 @@ void bwd_chain_kernel(
             // 16-B row-contiguous stores (a thread touches only its own
             // pieces, so no barrier inside the pass)
             gbf16* const dzo = (gbf16*)L.dz[l];
-#pragma unroll
-            for (int i = 0; i < NP; ++i) {
-                const int q = tid + i * NT;
-                const int r = q / PPR, col = (q % PPR) * 8;
+            CHAIN_FOR_PIECES(i, r, col) {
                 bf16x8 v = *(const bf16x8*)&tile[r][col];
 #pragma unroll
                 for (int e = 0; e < 8; ++e) {
@@ -225,68 +200,17 @@ void bwd_chain_kernel(
                     __syncthreads();
                 }
             } else {
-                // dh_{l-1} = dz_l · W_l: B fragments of this wave's columns
-                // straight from L2, U K-steps per load group
-                const gbf16* const wp =
-                    wt + (long)(wave * WN + lrow) * H + kch * 8;
-                bf16x8 b[U][FN], bn[U][FN];
-                auto load_b = [&](bf16x8(&bb)[U][FN], int t0) {
-#pragma unroll
-                    for (int u = 0; u < U; ++u)
-#pragma unroll
-                        for (int j = 0; j < FN; ++j)
-                            bb[u][j] = *(const gbf16x8*)(wp + (long)j * 16 * H +
-                                                         (t0 + u) * 32);
-                };
-                load_b(b, 0);
-                // fully unrolled with four waves; the eight-wave arm keeps
-                // the loop rolled to stay inside its 128 VGPRs (it spilled
-                // otherwise)
-#pragma unroll UNR
-                for (int t0 = 0; t0 < NSTEP; t0 += U) {
-                    if (t0 + U < NSTEP) load_b(bn, t0 + U);
-#pragma unroll
-                    for (int u = 0; u < U; ++u) {
-                        bf16x8 a_frag[FM];
-#pragma unroll
-                        for (int i = 0; i < FM; ++i)
-                            a_frag[i] = *(const bf16x8*)&tile[i * 16 + lrow]
-                                                            [(t0 + u) * 32 +
-                                                             kch * 8];
-#pragma unroll
-                        for (int i = 0; i < FM; ++i)
-#pragma unroll
-                            for (int j = 0; j < FN; ++j)
-                                acc[i][j] =
-                                    __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-                                        a_frag[i], b[u][j], acc[i][j], 0, 0, 0);
-                    }
-                    if (t0 + U < NSTEP) {
-#pragma unroll
-                        for (int u = 0; u < U; ++u)
-#pragma unroll
-                            for (int j = 0; j < FN; ++j) b[u][j] = bn[u][j];
-                    }
-                }
+                // dh_{l-1} = dz_l · W_l, W^T straight from L2
+                CHAIN_LAYER_MMA(acc, tile, wt)
             }
             __syncthreads();  // every wave has read the dz tile
-#pragma unroll
-            for (int i = 0; i < FM; ++i)
-#pragma unroll
-                for (int j = 0; j < FN; ++j)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r)
-                        tile[i * 16 + kch * 4 + r][wave * WN + j * 16 + lrow] =
-                            bf_bits(f2bf(acc[i][j][r]));
+            CHAIN_ACC_TO_TILE(acc, tile, )
             __syncthreads();
         }
 
         // every layer's dgrad was in the chain: the tile is dx
         if (dx != nullptr) {
-#pragma unroll
-            for (int i = 0; i < NP; ++i) {
-                const int q = tid + i * NT;
-                const int r = q / PPR, col = (q % PPR) * 8;
+            CHAIN_FOR_PIECES(i, r, col) {
                 if (row0 + r < M)
                     *(bf16x8*)&dx[(long)(row0 + r) * H + col] =
                         *(const bf16x8*)&tile[r][col];
@@ -298,30 +222,18 @@ void bwd_chain_kernel(
 
 namespace {
 
-template <int R, int NW, bool WLDS = false>
+// dz_scale: none, or the one float of the SCALED instantiation
+template <int R, int NW, bool WLDS = false, class... SA>
 void bwd_chain_launch(const void* probs, const void* target,
                       const void* Wt_head, void* dz_head,
                       const BwdChainLayers& L, int nlayers, void* dx, int M,
-                      int C, float inv_gb, hipStream_t st) {
+                      int C, float inv_gb, hipStream_t st, SA... dz_scale) {
     const int ntiles = cdiv(M, R);
-    hipLaunchKernelGGL((bwd_chain_kernel<R, NW, WLDS>), dim3(ntiles),
-                       dim3(NW * 64), 0, st, (const __bf16*)probs, (const __bf16*)target,
-                       (const __bf16*)Wt_head, (__bf16*)dz_head, L, nlayers,
-                       (__bf16*)dx, M, C, inv_gb, ntiles);
-}
-
-// the shipped arm with scaled dz
-void bwd_chain_launch_scaled(const void* probs, const void* target,
-                             const void* Wt_head, void* dz_head,
-                             const BwdChainLayers& L, int nlayers, void* dx,
-                             int M, int C, float inv_gb, float dz_scale,
-                             hipStream_t st) {
-    const int ntiles = cdiv(M, 64);
-    hipLaunchKernelGGL((bwd_chain_kernel<64, 8, false, true, float>),
-                       dim3(ntiles), dim3(8 * 64), 0, st,
-                       (const __bf16*)probs, (const __bf16*)target,
-                       (const __bf16*)Wt_head, (__bf16*)dz_head, L, nlayers,
-                       (__bf16*)dx, M, C, inv_gb, ntiles, dz_scale);
+    hipLaunchKernelGGL(
+        (bwd_chain_kernel<R, NW, WLDS, sizeof...(SA) == 1, SA...>),
+        dim3(ntiles), dim3(NW * 64), 0, st, (const __bf16*)probs,
+        (const __bf16*)target, (const __bf16*)Wt_head, (__bf16*)dz_head, L,
+        nlayers, (__bf16*)dx, M, C, inv_gb, ntiles, dz_scale...);
 }
 
 }  // namespace
@@ -332,23 +244,23 @@ void bwd_chain_launch_scaled(const void* probs, const void* target,
 // registers), 1 = W^T through LDS, built for (64, 8) only.
 // SS_BWD_CHAIN_ROWS / SS_BWD_CHAIN_WAVES / SS_BWD_CHAIN_WLDS (read once)
 // override the shipped choice for tuning.
-// scaled: dz_scale applies (any value, 1.0 included); only the shipped
-// arm is built with it.
-static bool bwd_chain_any(const void* probs, const void* target,
-                          const void* Wt_head, void* dz_head,
-                          const void* const* h, const void* const* wt,
-                          void* const* dz, int nlayers, void* dx, int M, int H,
-                          int C, float inv_gb, int rows, int waves, int w_lds,
-                          bool scaled, float dz_scale, hipStream_t st) {
+// dz_scale: 1.f runs the unscaled instantiations; any other value the
+// scaled one, which only the shipped arm is built with.
+bool ss_bwd_chain(const void* probs, const void* target, const void* Wt_head,
+                  void* dz_head, const void* const* h, const void* const* wt,
+                  void* const* dz, int nlayers, void* dx, int M, int H, int C,
+                  float inv_gb, int rows, int waves, int w_lds,
+                  float dz_scale, hipStream_t st) {
     if (M < 1 || H != 256 || C < 1 || C > 16 || nlayers < 1 ||
         nlayers > SS_BWD_CHAIN_MAX)
         return false;
     BwdChainLayers L = {};
     for (int l = 0; l < nlayers; ++l) {
         const bool last = l + 1 == nlayers;
-        if (!h[l] || !dz[l]) return false;
-        if (!last && !wt[l]) return false;
+        if (!aligned16(h[l]) || !aligned16(dz[l])) return false;
+        if (!last && !aligned16(wt[l])) return false;
         if (last && (wt[l] != nullptr) != (dx != nullptr)) return false;
+        if (last && dx && !(aligned16(wt[l]) && aligned16(dx))) return false;
         L.h[l] = h[l];
         L.wt[l] = wt[l];
         L.dz[l] = dz[l];
@@ -359,10 +271,11 @@ static bool bwd_chain_any(const void* probs, const void* target,
     if (!waves) waves = env_waves ? env_waves : 8;
     static const int env_wlds = env_int("SS_BWD_CHAIN_WLDS", 0);
     if (!w_lds) w_lds = env_wlds;
-    if (scaled) {
+    if (dz_scale != 1.f) {
         if (rows != 64 || waves != 8 || w_lds != 0) return false;
-        bwd_chain_launch_scaled(probs, target, Wt_head, dz_head, L, nlayers,
-                                dx, M, C, inv_gb, dz_scale, st);
+        bwd_chain_launch<64, 8, false>(probs, target, Wt_head, dz_head, L,
+                                       nlayers, dx, M, C, inv_gb, st,
+                                       dz_scale);
         return true;
     }
     if (w_lds == 1) {
@@ -371,39 +284,8 @@ static bool bwd_chain_any(const void* probs, const void* target,
                                       nlayers, dx, M, C, inv_gb, st);
         return true;
     }
-    if (rows == 32 && waves == 4)
-        bwd_chain_launch<32, 4>(probs, target, Wt_head, dz_head, L, nlayers,
-                                dx, M, C, inv_gb, st);
-    else if (rows == 32 && waves == 8)
-        bwd_chain_launch<32, 8>(probs, target, Wt_head, dz_head, L, nlayers,
-                                dx, M, C, inv_gb, st);
-    else if (rows == 64 && waves == 4)
-        bwd_chain_launch<64, 4>(probs, target, Wt_head, dz_head, L, nlayers,
-                                dx, M, C, inv_gb, st);
-    else if (rows == 64 && waves == 8)
-        bwd_chain_launch<64, 8>(probs, target, Wt_head, dz_head, L, nlayers,
-                                dx, M, C, inv_gb, st);
-    else
-        return false;
-    return true;
-}
-
-bool ss_bwd_chain(const void* probs, const void* target, const void* Wt_head,
-                  void* dz_head, const void* const* h, const void* const* wt,
-                  void* const* dz, int nlayers, void* dx, int M, int H, int C,
-                  float inv_gb, int rows, int waves, int w_lds,
-                  hipStream_t st) {
-    return bwd_chain_any(probs, target, Wt_head, dz_head, h, wt, dz, nlayers,
-                         dx, M, H, C, inv_gb, rows, waves, w_lds, false, 1.f,
-                         st);
-}
-
-bool ss_bwd_chain(const void* probs, const void* target, const void* Wt_head,
-                  void* dz_head, const void* const* h, const void* const* wt,
-                  void* const* dz, int nlayers, void* dx, int M, int H, int C,
-                  float inv_gb, int rows, int waves, int w_lds,
-                  float dz_scale, hipStream_t st) {
-    return bwd_chain_any(probs, target, Wt_head, dz_head, h, wt, dz, nlayers,
-                         dx, M, H, C, inv_gb, rows, waves, w_lds, true,
-                         dz_scale, st);
+    return with_chain_arm(rows, waves, [&](auto r, auto nw) {
+        bwd_chain_launch<r.value, nw.value>(probs, target, Wt_head, dz_head,
+                                            L, nlayers, dx, M, C, inv_gb, st);
+    });
 }

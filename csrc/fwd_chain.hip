@@ -35,15 +35,8 @@
 // first layer 256 (L1 = false) or a multiple of 8 (L1 = true), every
 // pointer 16-B aligned.
 
-#include "head_dev.h"
+#include "chain_dev.h"
 #include "launchers.h"
-
-#include <cstdint>
-
-// operands in the global address space: pointers that arrive inside the
-// by-value argument block would otherwise compile to FLAT accesses
-using gbf16 = __attribute__((address_space(1))) __bf16;
-using gbf16x8 = __attribute__((address_space(1))) bf16x8;
 
 // The layers of one launch, bottom first.  Passed BY VALUE: nothing to
 // upload, nothing to keep alive, and legal under graph capture.
@@ -53,9 +46,8 @@ struct FwdChainLayers {
     void* h[SS_FWD_CHAIN_MAX];        // post-ReLU output [M][256]
 };
 
-// R rows per tile, NW waves per block; wave w owns columns
-// [w*256/NW, +256/NW) of every layer's output.  Second launch bound =
-// waves per SIMD that two blocks on a CU need.
+// R rows per tile, NW waves per block (CHAIN_GEOMETRY).  Second launch
+// bound = waves per SIMD that two blocks on a CU need.
 template <int R, int NW, bool L1>
 __global__ __launch_bounds__(NW * 64, NW / 2)
 void fwd_chain_kernel(
@@ -65,24 +57,12 @@ void fwd_chain_kernel(
     const __bf16* __restrict__ b_head,  // [C]
     __bf16* __restrict__ probs,         // [M][C]
     int M, int K0, int C) {
-    constexpr int H = 256;
-    constexpr int NT = NW * 64;
-    constexpr int LDT = H + 8;          // padded tile row (bf16)
-    constexpr int PPR = H / 8;          // 16-B pieces per tile row
-    constexpr int NP = R * PPR / NT;    // pieces per thread
-    constexpr int FM = R / 16;          // 16-row fragments per tile
-    constexpr int WN = H / NW;          // columns per wave
-    constexpr int FN = WN / 16;
-    constexpr int NSTEP = H / 32;       // K-steps of a 256-wide layer
-    // K-steps per B load group: two where the accumulators leave room
-    constexpr int U = (FM * FN <= 8 && NW == 4) ? 2 : 1;
-    constexpr int UNR = NW == 4 ? NSTEP / U : 1;  // K-loop unroll count
+    CHAIN_GEOMETRY(R, NW);
     // first-layer stage: KC columns of x per chunk
     constexpr int KC = 128;
     constexpr int LDX = KC + 8;         // padded stage row (bf16)
     constexpr int XPR = KC / 8;         // 16-B pieces per stage row
     constexpr int XP = R * XPR / NT;    // stage pieces per thread
-    static_assert(R * PPR % NT == 0, "piece mapping");
     static_assert(R * XPR % NT == 0 && XP >= 1, "stage piece mapping");
     static_assert(FM <= NW, "one head fragment per wave");
 
@@ -108,24 +88,10 @@ void fwd_chain_kernel(
     // rounding), then the tile -> h_l as 16-B row-contiguous stores.
     // The caller has made sure that no wave still reads the tile.
     auto finish_layer = [&](int l, const float (&bv)[FN]) {
-#pragma unroll
-        for (int i = 0; i < FM; ++i)
-#pragma unroll
-            for (int j = 0; j < FN; ++j)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    float v = acc[i][j][r];
-                    v += bv[j];
-                    v = v > 0.f ? v : 0.f;
-                    tile[i * 16 + kch * 4 + r][wave * WN + j * 16 + lrow] =
-                        bf_bits(f2bf(v));
-                }
+        CHAIN_ACC_TO_TILE(acc, tile, v += bv[j]; v = v > 0.f ? v : 0.f)
         __syncthreads();
         gbf16* const ho = (gbf16*)L.h[l];
-#pragma unroll
-        for (int i = 0; i < NP; ++i) {
-            const int q = tid + i * NT;
-            const int r = q / PPR, col = (q % PPR) * 8;
+        CHAIN_FOR_PIECES(i, r, col) {
             if (row0 + r < M)
                 *(gbf16x8*)&ho[(long)(row0 + r) * H + col] =
                     *(const bf16x8*)&tile[r][col];
@@ -215,10 +181,7 @@ void fwd_chain_kernel(
         l = 1;
     } else {
         // ---- the input tile (rows past M as zeros: never stored)
-#pragma unroll
-        for (int i = 0; i < NP; ++i) {
-            const int q = tid + i * NT;
-            const int r = q / PPR, col = (q % PPR) * 8;
+        CHAIN_FOR_PIECES(i, r, col) {
             bf16x8 v = zero8();
             if (row0 + r < M) v = *(const bf16x8*)&x[(long)(row0 + r) * H + col];
             *(bf16x8*)&tile[r][col] = v;
@@ -232,45 +195,7 @@ void fwd_chain_kernel(
         float bv[FN];
         load_bias(l, bv);
         zero_acc();
-        // B fragments of this wave's columns straight from L2, U K-steps
-        // per load group
-        const gbf16* const wp = w + (long)(wave * WN + lrow) * H + kch * 8;
-        bf16x8 b[U][FN], bn[U][FN];
-        auto load_b = [&](bf16x8(&bb)[U][FN], int t0) {
-#pragma unroll
-            for (int u = 0; u < U; ++u)
-#pragma unroll
-                for (int j = 0; j < FN; ++j)
-                    bb[u][j] = *(const gbf16x8*)(wp + (long)j * 16 * H +
-                                                 (t0 + u) * 32);
-        };
-        load_b(b, 0);
-        // fully unrolled with four waves; the eight-wave arms keep the
-        // loop rolled to stay inside their 128 VGPRs, as bwd_chain_kernel
-#pragma unroll UNR
-        for (int t0 = 0; t0 < NSTEP; t0 += U) {
-            if (t0 + U < NSTEP) load_b(bn, t0 + U);
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                bf16x8 a_frag[FM];
-#pragma unroll
-                for (int i = 0; i < FM; ++i)
-                    a_frag[i] = *(const bf16x8*)&tile[i * 16 + lrow]
-                                                    [(t0 + u) * 32 + kch * 8];
-#pragma unroll
-                for (int i = 0; i < FM; ++i)
-#pragma unroll
-                    for (int j = 0; j < FN; ++j)
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-                            a_frag[i], b[u][j], acc[i][j], 0, 0, 0);
-            }
-            if (t0 + U < NSTEP) {
-#pragma unroll
-                for (int u = 0; u < U; ++u)
-#pragma unroll
-                    for (int j = 0; j < FN; ++j) b[u][j] = bn[u][j];
-            }
-        }
+        CHAIN_LAYER_MMA(acc, tile, w)
         __syncthreads();  // every wave has read the tile
         finish_layer(l, bv);
     }
@@ -300,22 +225,6 @@ void fwd_chain_kernel(
                           M, C)
     }
 }
-
-namespace {
-
-template <int R, int NW, bool L1>
-void fwd_chain_launch(const void* x, const FwdChainLayers& L, int nlayers,
-                      const void* W_head, const void* b_head, void* probs,
-                      int M, int K0, int C, hipStream_t st) {
-    hipLaunchKernelGGL((fwd_chain_kernel<R, NW, L1>), dim3(cdiv(M, R)),
-                       dim3(NW * 64), 0, st, (const __bf16*)x, L, nlayers,
-                       (const __bf16*)W_head, (const __bf16*)b_head,
-                       (__bf16*)probs, M, K0, C);
-}
-
-bool aligned16(const void* p) { return p && ((uintptr_t)p & 15) == 0; }
-
-}  // namespace
 
 // rows / waves: 0 = the shipped choice; (32, 4), (32, 8), (64, 4) and
 // (64, 8) are the measured arms (scripts/microbench_fwd_chain.py,
@@ -360,20 +269,16 @@ bool ss_fwd_chain(const void* x, const void* const* w, const void* const* b,
     }
     if (l1 != 1 && l1 != 2) return false;
     if (l1 == 1 && K0 != H) return false;
-#define FWD_CHAIN_ARM(RV, WV)                                                \
-    if (rows == RV && waves == WV) {                                         \
-        if (l1 == 2)                                                         \
-            fwd_chain_launch<RV, WV, true>(x, L, nlayers, W_head, b_head,    \
-                                           probs, M, K0, C, st);             \
-        else                                                                 \
-            fwd_chain_launch<RV, WV, false>(x, L, nlayers, W_head, b_head,   \
-                                            probs, M, K0, C, st);            \
-        return true;                                                         \
-    }
-    FWD_CHAIN_ARM(32, 4)
-    FWD_CHAIN_ARM(32, 8)
-    FWD_CHAIN_ARM(64, 4)
-    FWD_CHAIN_ARM(64, 8)
-#undef FWD_CHAIN_ARM
-    return false;
+    return with_chain_arm(rows, waves, [&](auto r, auto nw) {
+        constexpr int R = r.value, NW = nw.value;
+        with_bools(
+            [&](auto streamed) {
+                hipLaunchKernelGGL(
+                    (fwd_chain_kernel<R, NW, streamed.value>),
+                    dim3(cdiv(M, R)), dim3(NW * 64), 0, st, (const __bf16*)x,
+                    L, nlayers, (const __bf16*)W_head, (const __bf16*)b_head,
+                    (__bf16*)probs, M, K0, C);
+            },
+            l1 == 2);
+    });
 }

@@ -13,6 +13,12 @@
 
 #include <hip/hip_runtime.h>
 
+#include <cstdint>
+
+// Non-null and 16-byte aligned: what a kernel that moves 16-byte pieces
+// asks of a pointer.  The launchers and the bindings both test with it.
+inline bool aligned16(const void* p) { return p && ((uintptr_t)p & 15) == 0; }
+
 // ---- gemm.hip
 void ss_gemm_nt(const void* A, const void* B, const void* bias,
                 const void* mask, void* C, int M, int N, int K, bool relu,
@@ -77,15 +83,11 @@ bool ss_head_metrics(const void* probs, const void* target, void* acc,
 
 // ---- bwd_chain.hip
 // h / wt / dz: nlayers pointers each, top layer first (post-ReLU output,
-// W^T or null where the chain ends, masked gradient out).
+// W^T or null where the chain ends, masked gradient out).  dz_scale
+// (inverted dropout's 1/keep) scales every dz_l: 1.f is the unscaled
+// kernel, any other value is built for the shipped arm only, false for
+// the others.
 constexpr int SS_BWD_CHAIN_MAX = 8;
-bool ss_bwd_chain(const void* probs, const void* target, const void* Wt_head,
-                  void* dz_head, const void* const* h, const void* const* wt,
-                  void* const* dz, int nlayers, void* dx, int M, int H, int C,
-                  float inv_gb, int rows, int waves, int w_lds,
-                  hipStream_t stream);
-// The same with every dz_l scaled by dz_scale (inverted dropout's
-// 1/keep); built for the shipped arm only, false for the others.
 bool ss_bwd_chain(const void* probs, const void* target, const void* Wt_head,
                   void* dz_head, const void* const* h, const void* const* wt,
                   void* const* dz, int nlayers, void* dx, int M, int H, int C,

@@ -612,6 +612,35 @@ class Sequential(Module):
             return lin, head
         return None
 
+    # width of the chain kernels (csrc/fwd_chain.hip, csrc/bwd_chain.hip)
+    # and the most ReLU layers one launch of either takes
+    _CHAIN_WIDTH = 256
+    _CHAIN_MAX_LAYERS = 8
+
+    def _chain_head_pair(self):
+        """_head_pair() when its Linear has the head geometry of the
+        chain kernels (256 -> C <= 16, no fp8 forward), else None."""
+        pair = self._head_pair()
+        if pair is None or pair[0].in_dims != self._CHAIN_WIDTH \
+                or pair[0].out_dims > 16 or pair[0].fp8_fwd:
+            return None
+        return pair
+
+    def _chain_run(self):
+        """Indices, top first, of the consecutive Linear(activation=
+        "relu") layers with out_dims == 256 right under the head pair,
+        at most _CHAIN_MAX_LAYERS.  A chain plan is a prefix of it."""
+        run = []
+        for i in range(len(self.layers) - 3, -1, -1):
+            layer = self.layers[i]
+            if len(run) == self._CHAIN_MAX_LAYERS \
+                    or type(layer) is not Linear \
+                    or layer.activation != "relu" \
+                    or layer.out_dims != self._CHAIN_WIDTH:
+                break
+            run.append(i)
+        return run
+
     def _fwd_chain_plan(self):
         """Which layers the forward chain kernel (F.fwd_chain) takes
         together with the head: their indices, bottom first, or None
@@ -624,21 +653,12 @@ class Sequential(Module):
         when it ends the run and in_dims % 8 == 0.  No chain with
         dropout or an fp8 forward on a layer it would take.  Looks at
         the layer configuration only — no tensors, no device."""
-        pair = self._head_pair()
-        if pair is None or not F.fwd_chain_enabled() or not F.head_fused():
-            return None
-        lin = pair[0]
-        if lin.in_dims != self._CHAIN_WIDTH or lin.out_dims > 16 \
-                or lin.fp8_fwd:
+        if not F.fwd_chain_enabled() or not F.head_fused() \
+                or self._chain_head_pair() is None:
             return None
         plan = []
-        for i in range(len(self.layers) - 3, -1, -1):
+        for i in self._chain_run():
             layer = self.layers[i]
-            if len(plan) == self._CHAIN_MAX_LAYERS \
-                    or type(layer) is not Linear \
-                    or layer.activation != "relu" \
-                    or layer.out_dims != self._CHAIN_WIDTH:
-                break
             streamed = layer.in_dims != self._CHAIN_WIDTH
             if streamed and not (F.fwd_chain_l1() and layer.in_dims >= 8
                                  and layer.in_dims % 8 == 0):
@@ -748,11 +768,6 @@ class Sequential(Module):
         self._fire_grad_hooks(lin)
         return dx
 
-    # width of the backward chain kernel (csrc/bwd_chain.hip) and the
-    # most ReLU layers one launch takes
-    _CHAIN_WIDTH = 256
-    _CHAIN_MAX_LAYERS = 8
-
     def _bwd_chain_plan(self, mubatch_rows: int = 1):
         """Which layers the backward chain kernel (F.bwd_chain) takes:
         a list of (layer index, dgrad_in_chain), top layer first, or
@@ -766,22 +781,13 @@ class Sequential(Module):
         its dz from the kernel), or above the first layer that is no
         such Linear.  Looks at the layer configuration only — no
         tensors, no device."""
-        pair = self._head_pair()
-        if pair is None or mubatch_rows < 1 or not F.bwd_chain_enabled() \
-                or not F.head_fused() or F.head_wgrad_fused():
-            return None
-        lin = pair[0]
-        if lin.in_dims != self._CHAIN_WIDTH or lin.out_dims > 16 \
-                or lin.fp8_fwd:
+        if mubatch_rows < 1 or not F.bwd_chain_enabled() \
+                or not F.head_fused() or F.head_wgrad_fused() \
+                or self._chain_head_pair() is None:
             return None
         plan = []
-        for i in range(len(self.layers) - 3, -1, -1):
+        for i in self._chain_run():
             layer = self.layers[i]
-            if len(plan) == self._CHAIN_MAX_LAYERS \
-                    or type(layer) is not Linear \
-                    or layer.activation != "relu" \
-                    or layer.out_dims != self._CHAIN_WIDTH:
-                break
             need_dx = not (i == 0 and self._skip_input_grad)
             in_chain = need_dx and layer.in_dims == self._CHAIN_WIDTH
             if not in_chain and plan and not F.bwd_chain_dz_last():
@@ -826,13 +832,9 @@ class Sequential(Module):
         if not target.is_contiguous():
             target = target.contiguous()
         w_ts = [l.weight.compute_t() for l, (_, dg) in zip(chain, plan) if dg]
-        if self._has_dropout:
-            res = F.bwd_chain(s, target, lin.weight.compute_t(),
-                              head.global_batch_size, hs, w_ts,
-                              dz_scale=chain[0].dz_scale())
-        else:
-            res = F.bwd_chain(s, target, lin.weight.compute_t(),
-                              head.global_batch_size, hs, w_ts)
+        res = F.bwd_chain(s, target, lin.weight.compute_t(),
+                          head.global_batch_size, hs, w_ts,
+                          dz_scale=chain[0].dz_scale())
         if res is None:
             return False, None
         dz_head, dzs, dx = res

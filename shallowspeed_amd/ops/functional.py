@@ -599,16 +599,10 @@ def bwd_chain(probs, target, w_head_t, global_batch, hs, w_ts, rows=0,
     runs the unscaled kernel."""
     if not _is_gpu(probs):
         return None
-    if dz_scale == 1.0:
-        out = _ext_for(probs).bwd_chain(probs, target, w_head_t,
-                                        float(global_batch), list(hs),
-                                        list(w_ts), int(rows), int(waves),
-                                        int(w_lds))
-    else:
-        out = _ext_for(probs).bwd_chain(probs, target, w_head_t,
-                                        float(global_batch), list(hs),
-                                        list(w_ts), int(rows), int(waves),
-                                        int(w_lds), float(dz_scale))
+    out = _ext_for(probs).bwd_chain(probs, target, w_head_t,
+                                    float(global_batch), list(hs), list(w_ts),
+                                    int(rows), int(waves), int(w_lds),
+                                    float(dz_scale))
     if not out:
         return None
     n = len(hs)
