@@ -697,14 +697,16 @@ void sgd_multi(torch::Tensor desc, double lr, int64_t total,
                  (float)momentum, (float)weight_decay, cur_stream());
 }
 
+// omb1 / omb2 are 1 - beta1 / 1 - beta2 as the caller formed them in
+// double: rounded once here, never recomputed from the f32 betas.
 void adamw_multi(torch::Tensor desc, double lr, int64_t total, double beta1,
-                 double beta2, double eps, double weight_decay,
-                 double inv_bc1, double inv_bc2) {
+                 double beta2, double omb1, double omb2, double eps,
+                 double weight_decay, double inv_bc1, double inv_bc2) {
     check_table(desc, 9, "desc must be CUDA int64 [T,9]");
     ss_adamw_multi(desc.data_ptr(), (int)desc.size(0), (long)total,
-                   (float)lr, (float)beta1, (float)beta2, (float)eps,
-                   (float)weight_decay, (float)inv_bc1, (float)inv_bc2,
-                   cur_stream());
+                   (float)lr, (float)beta1, (float)beta2, (float)omb1,
+                   (float)omb2, (float)eps, (float)weight_decay,
+                   (float)inv_bc1, (float)inv_bc2, cur_stream());
 }
 
 void sgd_multi2(torch::Tensor desc, torch::Tensor bmap, double lr,
@@ -717,14 +719,15 @@ void sgd_multi2(torch::Tensor desc, torch::Tensor bmap, double lr,
 }
 
 void adamw_multi2(torch::Tensor desc, torch::Tensor bmap, double lr,
-                  double beta1, double beta2, double eps,
-                  double weight_decay, double inv_bc1, double inv_bc2) {
+                  double beta1, double beta2, double omb1, double omb2,
+                  double eps, double weight_decay, double inv_bc1,
+                  double inv_bc2) {
     check_table(desc, 9, "desc must be CUDA int64 [T,9]");
     check_table(bmap, 2, "bmap must be CUDA int64 [B,2]");
     ss_adamw_multi2(desc.data_ptr(), bmap.data_ptr(), (int)bmap.size(0),
-                    (float)lr, (float)beta1, (float)beta2, (float)eps,
-                    (float)weight_decay, (float)inv_bc1, (float)inv_bc2,
-                    cur_stream());
+                    (float)lr, (float)beta1, (float)beta2, (float)omb1,
+                    (float)omb2, (float)eps, (float)weight_decay,
+                    (float)inv_bc1, (float)inv_bc2, cur_stream());
 }
 
 torch::Tensor fused_mlp_argmax(torch::Tensor x, torch::Tensor desc,

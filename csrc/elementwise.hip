@@ -492,8 +492,8 @@ __global__ __launch_bounds__(256) void sgd_multi2_kernel(
 
 __global__ __launch_bounds__(256) void adamw_multi2_kernel(
     const long* __restrict__ desc, const long* __restrict__ bmap, float lr,
-    float beta1, float beta2, float eps, float weight_decay, float inv_bc1,
-    float inv_bc2) {
+    float beta1, float beta2, float omb1, float omb2, float eps,
+    float weight_decay, float inv_bc1, float inv_bc2) {
     const long* d = desc + bmap[(long)blockIdx.x * 2] * 9;
     const long base = bmap[(long)blockIdx.x * 2 + 1];
     const long n = d[4];
@@ -529,8 +529,8 @@ __global__ __launch_bounds__(256) void adamw_multi2_kernel(
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 const float g = g4[k];
-                const float m1 = beta1 * mav[k] + (1.f - beta1) * g;
-                const float v1 = beta2 * vav[k] + (1.f - beta2) * g * g;
+                const float m1 = beta1 * mav[k] + omb1 * g;
+                const float v1 = beta2 * vav[k] + omb2 * g * g;
                 mav[k] = m1;
                 vav[k] = v1;
                 float pv = mv[k];
@@ -551,8 +551,8 @@ __global__ __launch_bounds__(256) void adamw_multi2_kernel(
         } else {
             for (long q = e; q < n; ++q) {
                 const float g = grad[q];
-                const float m1 = beta1 * ma[q] + (1.f - beta1) * g;
-                const float v1 = beta2 * va[q] + (1.f - beta2) * g * g;
+                const float m1 = beta1 * ma[q] + omb1 * g;
+                const float v1 = beta2 * va[q] + omb2 * g * g;
                 ma[q] = m1;
                 va[q] = v1;
                 float pv = master[q];
@@ -607,13 +607,17 @@ __global__ __launch_bounds__(256) void transpose_bf16_kernel(
 
 __global__ __launch_bounds__(256) void adamw_multi_kernel(
     const long* __restrict__ desc, int ntensors, long total, float lr,
-    float beta1, float beta2, float eps, float weight_decay,
-    float inv_bc1, float inv_bc2) {
+    float beta1, float beta2, float omb1, float omb2, float eps,
+    float weight_decay, float inv_bc1, float inv_bc2) {
     // desc row (9 longs): [master, grad, lp, lp_t, numel, cols, start,
     // exp_avg, exp_avg_sq].  Decoupled weight decay (AdamW); bias
     // corrections inv_bc1 = 1/(1-beta1^t), inv_bc2 = 1/(1-beta2^t)
-    // precomputed on the host.  Re-emits the bf16 compute copy and
-    // the transposed bf16 copy, same as sgd_multi_kernel.
+    // precomputed on the host, and so are omb1 = 1-beta1, omb2 = 1-beta2:
+    // formed in double and rounded once.  1.f - beta2 from the f32 beta2
+    // is 0.00099998713 for 0.999, 1.3e-5 below the 0.001 that the CPU
+    // path and torch.optim.AdamW use, and exp_avg_sq is checkpointed.
+    // Re-emits the bf16 compute copy and the transposed bf16 copy, same
+    // as sgd_multi_kernel.
     long e = (long)blockIdx.x * 256 + threadIdx.x;
     const long stride = (long)gridDim.x * 256;
     for (; e < total; e += stride) {
@@ -629,8 +633,8 @@ __global__ __launch_bounds__(256) void adamw_multi_kernel(
         const float g = ((const float*)d[1])[i];
         float* ma = (float*)d[7];
         float* va = (float*)d[8];
-        const float m1 = beta1 * ma[i] + (1.f - beta1) * g;
-        const float v1 = beta2 * va[i] + (1.f - beta2) * g * g;
+        const float m1 = beta1 * ma[i] + omb1 * g;
+        const float v1 = beta2 * va[i] + omb2 * g * g;
         ma[i] = m1;
         va[i] = v1;
         float p = master[i];
@@ -660,12 +664,13 @@ void ss_sgd_multi2(const void* desc, const void* bmap, int nblocks,
 }
 
 void ss_adamw_multi2(const void* desc, const void* bmap, int nblocks,
-                     float lr, float beta1, float beta2, float eps,
-                     float weight_decay, float inv_bc1, float inv_bc2,
-                     hipStream_t st) {
+                     float lr, float beta1, float beta2, float omb1,
+                     float omb2, float eps, float weight_decay,
+                     float inv_bc1, float inv_bc2, hipStream_t st) {
     hipLaunchKernelGGL(adamw_multi2_kernel, dim3(nblocks), dim3(256), 0, st,
                        (const long*)desc, (const long*)bmap, lr, beta1,
-                       beta2, eps, weight_decay, inv_bc1, inv_bc2);
+                       beta2, omb1, omb2, eps, weight_decay, inv_bc1,
+                       inv_bc2);
 }
 
 void ss_transpose_bf16(const void* src, void* dst, int rows, int cols,
@@ -676,13 +681,15 @@ void ss_transpose_bf16(const void* src, void* dst, int rows, int cols,
 }
 
 void ss_adamw_multi(const void* desc, int ntensors, long total, float lr,
-                    float beta1, float beta2, float eps, float weight_decay,
-                    float inv_bc1, float inv_bc2, hipStream_t st) {
+                    float beta1, float beta2, float omb1, float omb2,
+                    float eps, float weight_decay, float inv_bc1,
+                    float inv_bc2, hipStream_t st) {
     long blocks = (total + 255) / 256;
     if (blocks > 1024) blocks = 1024;
     hipLaunchKernelGGL(adamw_multi_kernel, dim3((int)blocks), dim3(256), 0,
                        st, (const long*)desc, ntensors, total, lr, beta1,
-                       beta2, eps, weight_decay, inv_bc1, inv_bc2);
+                       beta2, omb1, omb2, eps, weight_decay, inv_bc1,
+                       inv_bc2);
 }
 
 void ss_sgd_multi(const void* desc, int ntensors, long total, float lr,

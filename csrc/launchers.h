@@ -133,14 +133,15 @@ void ss_transpose_bf16(const void* src, void* dst, int rows, int cols,
 void ss_sgd_multi(const void* desc, int ntensors, long total, float lr,
                   float momentum, float weight_decay, hipStream_t stream);
 void ss_adamw_multi(const void* desc, int ntensors, long total, float lr,
-                    float beta1, float beta2, float eps, float weight_decay,
-                    float inv_bc1, float inv_bc2, hipStream_t stream);
+                    float beta1, float beta2, float omb1, float omb2,
+                    float eps, float weight_decay, float inv_bc1,
+                    float inv_bc2, hipStream_t stream);
 void ss_sgd_multi2(const void* desc, const void* bmap, int nblocks, float lr,
                    float momentum, float weight_decay, hipStream_t stream);
 void ss_adamw_multi2(const void* desc, const void* bmap, int nblocks,
-                     float lr, float beta1, float beta2, float eps,
-                     float weight_decay, float inv_bc1, float inv_bc2,
-                     hipStream_t stream);
+                     float lr, float beta1, float beta2, float omb1,
+                     float omb2, float eps, float weight_decay,
+                     float inv_bc1, float inv_bc2, hipStream_t stream);
 
 // ---- norm.hip
 void ss_ln_fwd(const void* x, const void* gamma, const void* beta, void* y,

@@ -22,6 +22,28 @@ import torch
 from ..ops._ext import load_ext
 
 
+# Parameter count from which step() takes the block-map (v2) kernels:
+# below it the v1 grid-stride kernels win (6.8 vs 18.6 µs at the
+# 270K-param flagship), above it the per-element descriptor search loses
+# (8.2 vs ~0.5 ms at 523M params).  Read at every step.
+BLOCKMAP_MIN_ELEMS = 1 << 22
+
+
+def _check_blockmap_alignment(rows):
+    """What the v2 kernels assume of a descriptor table (the rows of
+    _build_desc): they read and write master and optimizer state as
+    float4 and the bf16 copy as ushort4, at element offsets that are
+    multiples of 4.  A misaligned view would not fault, it would be
+    read as some other float4.  The grad view may sit at any offset
+    (the kernels fall back to scalar loads) and lp_t is written one
+    element at a time."""
+    for r in rows:
+        for ptr in [r[0]] + list(r[7:]):
+            assert ptr % 16 == 0, \
+                f"master / optimizer state must be 16-byte aligned: {ptr:#x}"
+        assert r[2] % 8 == 0, f"lp must be 8-byte aligned: {r[2]:#x}"
+
+
 def _split_tiled_transposes(params):
     """Large 2-D weights whose transposed bf16 copy should be emitted
     by the tiled transpose kernel instead of the fused optimizer's
@@ -99,6 +121,7 @@ class SGD:
             ])
             start += t.numel()
         self._total = start
+        _check_blockmap_alignment(rows)
         cpu = torch.tensor(rows, dtype=torch.int64)
         self._desc = cpu.to(self.params[0].data.device)
         self._desc_cpu = cpu
@@ -113,7 +136,7 @@ class SGD:
             ext = load_ext(required=True)
             if self._desc is None:
                 self._build_desc()
-            if self._total >= (1 << 22):
+            if self._total >= BLOCKMAP_MIN_ELEMS:
                 # blockmap kernel: wins at large param counts (binary
                 # search chain removed; 8.2→~0.5 ms at 523M params)
                 ext.sgd_multi2(self._desc, self._bmap, self.lr,
@@ -196,6 +219,7 @@ class AdamW:
             ])
             start += t.numel()
         self._total = start
+        _check_blockmap_alignment(rows)
         cpu = torch.tensor(rows, dtype=torch.int64)
         self._desc = cpu.to(self.params[0].data.device)
         self._bmap = _build_blockmap(self.params, self._desc.device)
@@ -213,14 +237,17 @@ class AdamW:
             ext = load_ext(required=True)
             if self._desc is None:
                 self._build_desc()
-            if self._total >= (1 << 22):
+            # 1 - beta goes down as its own argument, formed here in
+            # double like the CPU path's below: the kernels' former
+            # 1.f - beta2 from the f32-rounded beta2 was 1.3e-5 low.
+            if self._total >= BLOCKMAP_MIN_ELEMS:
                 ext.adamw_multi2(self._desc, self._bmap, self.lr, b1, b2,
-                                 self.eps, self.weight_decay, inv_bc1,
-                                 inv_bc2)
+                                 1 - b1, 1 - b2, self.eps,
+                                 self.weight_decay, inv_bc1, inv_bc2)
             else:
                 ext.adamw_multi(self._desc, self.lr, self._total, b1, b2,
-                                self.eps, self.weight_decay, inv_bc1,
-                                inv_bc2)
+                                1 - b1, 1 - b2, self.eps,
+                                self.weight_decay, inv_bc1, inv_bc2)
             for _, lp, lpt in self._tiled_t:
                 ext.transpose_bf16(lp, lpt)
         else:
