@@ -267,7 +267,8 @@ void wgrad_tn_256(torch::Tensor dy, torch::Tensor x, torch::Tensor gw) {
 }
 
 void wgrad_tn(torch::Tensor dy, torch::Tensor x, torch::Tensor gw,
-              torch::Tensor gb, torch::Tensor mask, int64_t split_k) {
+              torch::Tensor gb, torch::Tensor mask, int64_t split_k,
+              int64_t stages) {
     check_bf16(dy, "dy");
     check_bf16(x, "x");
     check_f32(gw, "gw");
@@ -278,11 +279,12 @@ void wgrad_tn(torch::Tensor dy, torch::Tensor x, torch::Tensor gw,
     TORCH_CHECK(!mask_p || mask.sizes() == dy.sizes(), "mask must match dy");
     void* gb_p = opt_f32(gb, "gb");
     TORCH_CHECK(!gb_p || gb.numel() == Mo, "gb size");
+    TORCH_CHECK(stages >= 0 && stages <= 2, "stages must be 0, 1 or 2");
     // bias grad is FUSED into the wgrad kernel (n-tile-0 blocks sum
     // the already-masked LDS dY tile) — no separate colsum launch or
     // extra dY read on the hot path.
     ss_wgrad_tn(dy.data_ptr(), x.data_ptr(), mask_p, gw.data_ptr(), gb_p, Mo,
-                N, Kb, (int)split_k, cur_stream());
+                N, Kb, (int)split_k, (int)stages, cur_stream());
 }
 
 void wgrad_tn_multi(torch::Tensor chunk_table, int64_t nchunks,
@@ -776,7 +778,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "MX-fp8 256-tile GEMM: C=bf16(A@B^T) (+bias)(+relu)");
     m.def("gemm_nt_f8_q", &gemm_nt_f8_q,
           "MX-fp8 GEMM with FUSED output quantization -> (e4m3, scales)");
-    m.def("wgrad_tn", &wgrad_tn, "gW += (dy⊙mask)^T @ x; gb += colsum (fused)");
+    m.def("wgrad_tn", &wgrad_tn,
+          "gW += (dy⊙mask)^T @ x; gb += colsum (fused); stages = LDS "
+          "staging sets of the K loop (0 = the launcher's choice)",
+          py::arg("dy"), py::arg("x"), py::arg("gw"), py::arg("gb"),
+          py::arg("mask"), py::arg("split_k"), py::arg("stages") = 0);
     m.def("colsum", &colsum, "standalone column sum (bias grad)");
     m.def("wgrad_tn_multi", &wgrad_tn_multi,
           "chunked (deferred-µbatch) wgrad: one launch, many (dy,x) pairs");

@@ -61,8 +61,10 @@ bool ss_gemm_nt_f8_q(const void* A, const void* Asc, const void* B,
                      int M, int N, int K, bool relu, hipStream_t stream);
 
 // ---- wgrad.hip / wgrad256.hip
+// stages: LDS staging sets of the K loop, 1 or 2; 0 = the launcher's
+// choice (SS_WGRAD_STAGES, else the measured default).
 void ss_wgrad_tn(const void* dY, const void* X, const void* mask, void* gW,
-                 void* gb, int Mo, int N, int Kb, int split_k,
+                 void* gb, int Mo, int N, int Kb, int split_k, int stages,
                  hipStream_t stream);
 void ss_wgrad_tn_multi(const void* chunk_table, int nchunks, bool has_mask,
                        void* gW, void* gb, int Mo, int N, int Kb_chunk,
