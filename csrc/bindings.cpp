@@ -557,16 +557,30 @@ std::vector<torch::Tensor> bwd_chain(torch::Tensor probs, torch::Tensor target,
 // the first layer streams it).  Returns [h_0, ..., h_{n-1}, probs], or
 // an EMPTY list, with nothing allocated or launched, when the inputs are
 // outside the kernel's contract: the caller then takes the per-layer
-// path.
+// path.  zero: a contiguous f32 tensor on x's device that the launch
+// also fills with zeros (the step's flat gradient buffer), or None; it
+// is left untouched when the launch is refused.
 std::vector<torch::Tensor> fwd_chain(torch::Tensor x,
                                      std::vector<torch::Tensor> ws,
                                      std::vector<torch::Tensor> bs,
                                      torch::Tensor w_head,
                                      torch::Tensor b_head, int64_t rows,
-                                     int64_t waves, int64_t l1) {
+                                     int64_t waves, int64_t l1,
+                                     int64_t kloop,
+                                     std::optional<torch::Tensor> zero) {
     constexpr int64_t H = 256;
     const int64_t n = (int64_t)ws.size();
     if (n < 1 || n > SS_FWD_CHAIN_MAX || (int64_t)bs.size() != n) return {};
+    if (kloop < 0 || kloop > 2) return {};
+    void* zero_p = nullptr;
+    int64_t zero_bytes = 0;
+    if (zero.has_value() && zero->defined() && zero->numel() > 0) {
+        if (zero->scalar_type() != torch::kFloat32 || !zero->is_contiguous() ||
+            zero->device() != x.device())
+            return {};
+        zero_p = zero->data_ptr();
+        zero_bytes = zero->numel() * 4;
+    }
     if (!plain(x, 2) || !plain(w_head, 2) || !plain(b_head, 1)) return {};
     const int64_t M = x.size(0), K0 = x.size(1), C = w_head.size(0);
     if (M > INT_MAX / 1024 || K0 % 8 != 0 || C > 16 ||
@@ -595,7 +609,7 @@ std::vector<torch::Tensor> fwd_chain(torch::Tensor x,
     if (!ss_fwd_chain(x.data_ptr(), wp, bp, hp, (int)n, w_head.data_ptr(),
                       b_head.data_ptr(), out.back().data_ptr(), (int)M,
                       (int)K0, (int)H, (int)C, (int)rows, (int)waves, (int)l1,
-                      cur_stream()))
+                      (int)kloop, zero_p, (long)zero_bytes, cur_stream()))
         return {};
     return out;
 }
@@ -829,7 +843,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "[h_l..., probs], or [] outside the contract",
           py::arg("x"), py::arg("ws"), py::arg("bs"), py::arg("w_head"),
           py::arg("b_head"), py::arg("rows") = 0, py::arg("waves") = 0,
-          py::arg("l1") = 0);
+          py::arg("l1") = 0, py::arg("kloop") = 0,
+          py::arg("zero") = py::none());
     m.def("head_metrics", &head_metrics,
           "metric totals of (probs, target) into a slotted accumulator",
           py::arg("probs"), py::arg("target"), py::arg("acc"),

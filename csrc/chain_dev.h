@@ -88,6 +88,46 @@ using gbf16x8 = __attribute__((address_space(1))) bf16x8;
         }                                                                    \
     }
 
+// The same layer, same MFMAs in the same order, with the B fragments
+// CHAIN_B_AHEAD K-steps ahead: a ring of CHAIN_B_AHEAD + 1 named register
+// sets, the loop fully unrolled so that every set index is a constant
+// and no set is ever copied into another.  Step t's MFMAs wait for set
+// t alone; the loads of steps t+1 .. t+CHAIN_B_AHEAD stay in flight
+// under them.  (CHAIN_LAYER_MMA hands bn over to b at the end of a step;
+// that copy waits for the next step's loads, so its lookahead is one
+// step in the source and none in the instructions.)  For the eight-wave
+// arms of fwd_chain_kernel.
+#define CHAIN_B_AHEAD 3
+#define CHAIN_LAYER_MMA_AHEAD(acc, tile, w)                                  \
+    {                                                                        \
+        const gbf16* const wp = w + (long)(wave * WN + lrow) * H + kch * 8;  \
+        bf16x8 bq[CHAIN_B_AHEAD + 1][FN];                                    \
+        auto load_b = [&](bf16x8(&bb)[FN], int t) {                          \
+            _Pragma("unroll") for (int j = 0; j < FN; ++j)                   \
+                bb[j] = *(const gbf16x8*)(wp + (long)j * 16 * H + t * 32);   \
+        };                                                                   \
+        _Pragma("unroll") for (int t = 0; t < CHAIN_B_AHEAD; ++t)            \
+            load_b(bq[t], t);                                                \
+        _Pragma("unroll") for (int t = 0; t < NSTEP; ++t) {                  \
+            if (t + CHAIN_B_AHEAD < NSTEP)                                   \
+                load_b(bq[(t + CHAIN_B_AHEAD) % (CHAIN_B_AHEAD + 1)],        \
+                       t + CHAIN_B_AHEAD);                                   \
+            /* fences: left alone, the scheduler sinks the loads to just */  \
+            /* above their first use */                                      \
+            __builtin_amdgcn_sched_barrier(0);                               \
+            bf16x8 a_frag[FM];                                               \
+            _Pragma("unroll") for (int i = 0; i < FM; ++i)                   \
+                a_frag[i] = *(const bf16x8*)&tile[i * 16 + lrow]             \
+                                                [t * 32 + kch * 8];          \
+            _Pragma("unroll") for (int i = 0; i < FM; ++i)                   \
+                _Pragma("unroll") for (int j = 0; j < FN; ++j)               \
+                    acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(     \
+                        a_frag[i], bq[t % (CHAIN_B_AHEAD + 1)][j],           \
+                        acc[i][j], 0, 0, 0);                                 \
+            __builtin_amdgcn_sched_barrier(0);                               \
+        }                                                                    \
+    }
+
 // acc[FM][FN] -> tile, each element rounded once by f2bf.  EPILOGUE is
 // the caller's statement(s) on `float v` between the accumulator and the
 // rounding (j is the column fragment, for a per-column operand), or

@@ -101,11 +101,17 @@ bool ss_bwd_chain(const void* probs, const void* target, const void* Wt_head,
 // bias, post-ReLU output).  x is the input of layer 0, [M][K0]; l1
 // selects how the chain starts (0 = shipped choice, 1 = from a stored
 // 256-wide activation, 2 = the first layer streams x, K0 % 8 == 0).
+// kloop selects the K loops (0 = shipped choice, 1 = B one step ahead,
+// 2 = B three steps ahead in named register sets; eight waves only).
+// zero_ptr / zero_bytes: memory the launch also fills with zeros (the
+// step's gradient buffer), 4-B aligned and a multiple of 4 bytes, or
+// nullptr / 0.
 constexpr int SS_FWD_CHAIN_MAX = 8;
 bool ss_fwd_chain(const void* x, const void* const* w, const void* const* b,
                   void* const* h, int nlayers, const void* W_head,
                   const void* b_head, void* probs, int M, int K0, int H, int C,
-                  int rows, int waves, int l1, hipStream_t stream);
+                  int rows, int waves, int l1, int kloop, void* zero_ptr,
+                  long zero_bytes, hipStream_t stream);
 
 // ---- fused_mlp.hip
 bool ss_fused_mlp_fwd(const void* x, const void* desc, int M, int in_dim,

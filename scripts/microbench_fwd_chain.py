@@ -11,7 +11,13 @@ it replaces.  Needs a GPU.
 Times are device-event time over back-to-back launches (launch gaps
 included), per call in µs; the arms alternate inside every round and
 the table gives the best and the median round, so they compare with one
-another, not with profiler kernel times."""
+another, not with profiler kernel times.
+
+  starts      the shipped eight-wave arms from x, the K loops side by
+              side (kloop 1 = B one step ahead, 2 = three steps ahead),
+              at M = 16384, 32768 (two rounds of 64-row tiles) and 4096
+              (32 rows), with and without the gradient buffer's zeros
+              riding in the launch (against the memset launch)"""
 import statistics
 import sys
 
@@ -46,7 +52,7 @@ def bench(arms):
             times[name].append(a.elapsed_time(b) / ITERS * 1e3)
     for name, ts in times.items():
         print(f"{name:44s}: best {min(ts):6.1f}  median "
-              f"{statistics.median(ts):6.1f} us")
+              f"{statistics.median(ts):6.1f}  max {max(ts):6.1f} us")
 
 
 M, H, C, IN0 = 16384, 256, 10, 784
@@ -99,3 +105,23 @@ for arm in ARMS:
         lambda a=arm: F.fwd_chain(x, [w1] + ws, [b1] + bs, w_head, b_head,
                                   *a, l1=2))
 bench(arms)
+
+# the flagship's flat gradient buffer: 335114 floats
+grads = torch.empty(784 * 256 + 2 * 256 * 256 + 2560 + 3 * 256 + 10,
+                    device=dev)
+for m, rows in ((16384, 64), (32768, 64), (4096, 32)):
+    xm = rnd(m, IN0)
+    print(f"starts from x, M={m} rows={rows} waves=8")
+    arms = {}
+    for kloop in (1, 2):
+        arms[f"l1=2 kloop={kloop}"] = (
+            lambda k=kloop: F.fwd_chain(xm, [w1] + ws, [b1] + bs, w_head,
+                                        b_head, rows, 8, l1=2, kloop=k))
+    arms["grads.zero_() + l1=2 kloop=2"] = (
+        lambda: (grads.zero_(),
+                 F.fwd_chain(xm, [w1] + ws, [b1] + bs, w_head, b_head, rows,
+                             8, l1=2, kloop=2)))
+    arms["l1=2 kloop=2 zero=grads"] = (
+        lambda: F.fwd_chain(xm, [w1] + ws, [b1] + bs, w_head, b_head, rows,
+                            8, l1=2, kloop=2, zero=grads))
+    bench(arms)

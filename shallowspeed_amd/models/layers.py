@@ -678,11 +678,18 @@ class Sequential(Module):
         if not F.head_fused_ok(x, lin):
             return None
         chain = [self.layers[i] for i in plan]
+        # a deferred zero_grad rides in this launch (same stream, ahead
+        # of every kernel that adds to the gradients)
+        zero = self._flat_grad if getattr(self, "_zero_pending", False) \
+            and self._flat_grad.device == x.device else None
         res = F.fwd_chain(x, [l.weight.compute() for l in chain],
                           [l.bias.compute() for l in chain],
-                          lin.weight.compute(), lin.bias.compute())
+                          lin.weight.compute(), lin.bias.compute(),
+                          zero=zero)
         if res is None:
             return None
+        if zero is not None:
+            self._zero_pending = False
         hs, probs = res
         for layer, h in zip(chain, hs):
             layer._stash("x", mubatch_id, x)
@@ -707,6 +714,8 @@ class Sequential(Module):
             first = plan[0]
         else:
             first = 0
+        # no chain launch took a deferred zero_grad along
+        self._settle_zero_grad()
         for layer in self.layers[first:n_plain]:
             x = layer.forward(x, mubatch_id)
         if pair:
@@ -860,6 +869,7 @@ class Sequential(Module):
         return True, dx
 
     def backward(self, dout, mubatch_id: int = 0):
+        self._settle_zero_grad()
         d = dout
         last = len(self.layers) - 1
         pair = self._head_pair()
@@ -906,12 +916,30 @@ class Sequential(Module):
     def parameters(self):
         return [p for layer in self.layers for p in layer.parameters()]
 
-    def zero_grad(self):
-        if getattr(self, "_flat_grad", None) is not None:
-            self._flat_grad.zero_()
-        else:
+    def zero_grad(self, defer=False):
+        """Zero every gradient.  defer=True lets the next forward chain
+        launch write the zeros (F.fwd_chain(zero=...)) instead of a
+        memset launch of its own: the buffer is only marked, and holds
+        its old values until that forward, or until _settle_zero_grad()
+        at whatever reads or adds to the gradients first.  Deferred only
+        with a flat gradient buffer on the GPU and a forward chain plan
+        (F.fwd_zero_grads() on); the memset is done at once otherwise."""
+        flat = getattr(self, "_flat_grad", None)
+        self._zero_pending = False
+        if flat is None:
             for layer in self.layers:
                 layer.zero_grad()
+        elif defer and flat.is_cuda and F.fwd_zero_grads() \
+                and self._fwd_chain_plan():
+            self._zero_pending = True
+        else:
+            flat.zero_()
+
+    def _settle_zero_grad(self):
+        """The memset a zero_grad(defer=True) still owes, now."""
+        if getattr(self, "_zero_pending", False):
+            self._zero_pending = False
+            self._flat_grad.zero_()
 
     def train(self):
         self._training = True
@@ -971,6 +999,7 @@ class Sequential(Module):
         final (AllReduce) backward flushes in-backward via
         _flush_in_backward; leftovers here mean a schedule never issued
         BackwardGradAllReduce."""
+        self._settle_zero_grad()
         n = 0
         for layer in reversed(self.layers):
             if hasattr(layer, "flush_wgrad") and layer._wgrad_pending:
@@ -1002,6 +1031,7 @@ class Sequential(Module):
             p.grad = flat[off:off + n].view(p.data.shape)
             off += n
         self._flat_grad = flat
+        self._zero_pending = False
         return self
 
 

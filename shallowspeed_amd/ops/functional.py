@@ -170,6 +170,25 @@ def fwd_chain_l1() -> bool:
     return _FWD_CHAIN_L1
 
 
+_FWD_ZERO_GRADS = None
+
+
+def fwd_zero_grads() -> bool:
+    """Whether Sequential.zero_grad(defer=True) may leave the memset of
+    the flat gradient buffer to the next forward chain launch.  Default
+    OFF, SS_FWD_ZERO_GRADS=1 (read once) turns it on: at the flagship it
+    measured 2.4 us of a 124 us step, 7 kernels instead of 8, every run
+    faster than every run without it, but under the bar of five times
+    the run-to-run spread that a change has to clear to ship switched on
+    (profiles/r14_fwd_loader.md section 5)."""
+    global _FWD_ZERO_GRADS
+    if _FWD_ZERO_GRADS is None:
+        import os
+
+        _FWD_ZERO_GRADS = os.environ.get("SS_FWD_ZERO_GRADS", "0") == "1"
+    return _FWD_ZERO_GRADS
+
+
 def _is_gpu(t: torch.Tensor) -> bool:
     return t.is_cuda
 
@@ -609,7 +628,8 @@ def bwd_chain(probs, target, w_head_t, global_batch, hs, w_ts, rows=0,
     return out[0], out[1:1 + n], (out[1 + n] if len(w_ts) == n else None)
 
 
-def fwd_chain(x, ws, bs, w_head, b_head, rows=0, waves=0, l1=0):
+def fwd_chain(x, ws, bs, w_head, b_head, rows=0, waves=0, l1=0, kloop=0,
+              zero=None):
     """The ReLU layers under the fused head and the head forward in one
     kernel (GPU only, csrc/fwd_chain.hip).
 
@@ -624,11 +644,18 @@ def fwd_chain(x, ws, bs, w_head, b_head, rows=0, waves=0, l1=0):
     inputs are outside the kernel's contract (the caller takes the
     per-layer path).  rows / waves select the measured arms, l1 how the
     chain starts (1: from a stored 256-wide activation, 2: streaming
-    x); 0 is the shipped choice."""
+    x), kloop its K loops (1: B fragments one step ahead, 2: three
+    steps ahead, eight waves only); 0 is the shipped choice.
+
+    zero: a contiguous f32 tensor on x's device, or None.  The launch
+    fills it with zeros as well (the step's flat gradient buffer: see
+    Sequential.zero_grad(defer=True)); when the launch is refused it is
+    left as it was."""
     if not _is_gpu(x):
         return None
     out = _ext_for(x).fwd_chain(x, list(ws), list(bs), w_head, b_head,
-                                int(rows), int(waves), int(l1))
+                                int(rows), int(waves), int(l1), int(kloop),
+                                zero)
     if not out:
         return None
     return out[:-1], out[-1]

@@ -453,11 +453,19 @@ class Worker:
 
     # ------------------------------------------------- instruction impls
     def _zero_grad(self, cmd):
-        self.model.zero_grad()
+        # the first forward chain launch of the step writes the zeros,
+        # unless the µbatch forwards run on side streams: a second
+        # stream's kernels could then add to the buffer ahead of them
+        if hasattr(self.model, "_settle_zero_grad"):
+            self.model.zero_grad(defer=not getattr(self, "_mu_par", False))
+        else:
+            self.model.zero_grad()
         self._mu_fork()
 
     def _optimizer_step(self, cmd):
         self._mu_join()
+        if hasattr(self.model, "_settle_zero_grad"):
+            self.model._settle_zero_grad()  # a step without a forward
         if getattr(self, "_defer_active", False):
             # normally a no-op: the AllReduce backward flushed every
             # layer mid-backward (_flush_in_backward).  Leftovers mean
