@@ -306,6 +306,83 @@ void wgrad_tn_multi(torch::Tensor chunk_table, int64_t nchunks,
                       (int)split_k, cur_stream());
 }
 
+// Grouped launch.  A problem is (dy, x, gw, gb); gb may be None or empty.
+using WgradGroupProblem = std::tuple<torch::Tensor, torch::Tensor,
+                                     torch::Tensor,
+                                     std::optional<torch::Tensor>>;
+
+std::vector<int> wgrad_group_splits(
+    const std::optional<std::vector<int64_t>>& splits, size_t n) {
+    std::vector<int> s(n, 0);
+    if (!splits) return s;
+    TORCH_CHECK(splits->size() == n, "splits: one per problem");
+    for (size_t i = 0; i < n; ++i) {
+        const int64_t v = (*splits)[i];
+        TORCH_CHECK(v == 0 || (v >= 2 && v <= INT_MAX),
+                    "split must be 0 (the group rule) or >= 2");
+        s[i] = (int)v;
+    }
+    return s;
+}
+
+void wgrad_tn_group(std::vector<WgradGroupProblem> problems,
+                    std::optional<std::vector<int64_t>> splits) {
+    // every check before the first launch: a refused call touches nothing
+    std::vector<WgradProblem> p;
+    for (const auto& [dy, x, gw, gb] : problems) {
+        check_bf16(dy, "dy");
+        check_bf16(x, "x");
+        check_f32(gw, "gw");
+        TORCH_CHECK(dy.dim() == 2 && x.dim() == 2 && gw.dim() == 2,
+                    "dy, x, gw must be 2-D");
+        const int Kb = dy.size(0), Mo = dy.size(1), N = x.size(1);
+        TORCH_CHECK(x.size(0) == Kb, "batch mismatch");
+        TORCH_CHECK(gw.size(0) == Mo && gw.size(1) == N, "gw shape");
+        void* gb_p = gb ? opt_f32(*gb, "gb") : nullptr;
+        TORCH_CHECK(!gb_p || gb->numel() == Mo, "gb size");
+        p.push_back({dy.data_ptr(), x.data_ptr(), gw.data_ptr(), gb_p, Mo, N,
+                     Kb});
+    }
+    const std::vector<int> s = wgrad_group_splits(splits, p.size());
+    if (p.empty()) return;
+    TORCH_CHECK(ss_wgrad_tn_group(p.data(), (int)p.size(), s.data(),
+                                  cur_stream()),
+                "wgrad_tn_group: bad shape, split or pointer");
+}
+
+// The launches wgrad_tn_group makes for these (Kb, Mo, N) shapes: per
+// launch (problem indices, splits, block counts).  Host only.
+std::vector<std::tuple<std::vector<int64_t>, std::vector<int64_t>,
+                       std::vector<int64_t>>>
+wgrad_group_plan(std::vector<std::tuple<int64_t, int64_t, int64_t>> shapes,
+                 std::optional<std::vector<int64_t>> splits) {
+    std::vector<WgradProblem> p;
+    for (const auto& [Kb, Mo, N] : shapes) {
+        TORCH_CHECK(Kb >= 1 && Mo >= 1 && N >= 1 && Kb <= INT_MAX &&
+                        Mo <= INT_MAX && N <= INT_MAX,
+                    "shape (Kb, Mo, N)");
+        p.push_back({nullptr, nullptr, nullptr, nullptr, (int)Mo, (int)N,
+                     (int)Kb});
+    }
+    const std::vector<int> s = wgrad_group_splits(splits, p.size());
+    std::vector<WgradGroupLaunch> plan(p.size());
+    const int nl =
+        ss_wgrad_group_plan(p.data(), (int)p.size(), s.data(), plan.data());
+    TORCH_CHECK(nl >= 0, "wgrad_group_plan: bad shape or split");
+    std::vector<std::tuple<std::vector<int64_t>, std::vector<int64_t>,
+                           std::vector<int64_t>>> out;
+    for (int l = 0; l < nl; ++l) {
+        std::vector<int64_t> idx, sp, bl;
+        for (int k = 0; k < plan[l].count; ++k) {
+            idx.push_back(plan[l].first + k);
+            sp.push_back(plan[l].split[k]);
+            bl.push_back(plan[l].blocks[k]);
+        }
+        out.emplace_back(idx, sp, bl);
+    }
+    return out;
+}
+
 torch::Tensor colsum(torch::Tensor dy, torch::Tensor mask) {
     check_bf16(dy, "dy");
     const void* mask_p = opt_bf16(mask, "mask");
@@ -797,6 +874,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "staging sets of the K loop (0 = the launcher's choice)",
           py::arg("dy"), py::arg("x"), py::arg("gw"), py::arg("gb"),
           py::arg("mask"), py::arg("split_k"), py::arg("stages") = 0);
+    m.def("wgrad_tn_group", &wgrad_tn_group,
+          "unmasked wgrads of a list of (dy, x, gw, gb): consecutive "
+          "problems of one tile configuration share a launch",
+          py::arg("problems"), py::arg("splits") = py::none());
+    m.def("wgrad_group_plan", &wgrad_group_plan,
+          "launches of wgrad_tn_group for (Kb, Mo, N) shapes: per launch "
+          "(problem indices, splits, block counts)",
+          py::arg("shapes"), py::arg("splits") = py::none());
     m.def("colsum", &colsum, "standalone column sum (bias grad)");
     m.def("wgrad_tn_multi", &wgrad_tn_multi,
           "chunked (deferred-µbatch) wgrad: one launch, many (dy,x) pairs");

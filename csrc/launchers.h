@@ -72,6 +72,36 @@ void ss_wgrad_tn_multi(const void* chunk_table, int nchunks, bool has_mask,
 bool ss_wgrad_tn_256(const void* dY, const void* X, void* gW, int Mo, int N,
                      int Kb, hipStream_t stream);
 
+// Grouped launch: independent unmasked problems, side by side.
+constexpr int SS_WGRAD_GROUP_MAX = 8;  // problems per launch
+struct WgradProblem {
+    const void* dY;  // [Kb][Mo] bf16
+    const void* X;   // [Kb][N] bf16
+    void* gW;        // [Mo][N] f32, +=
+    void* gb;        // [Mo] f32 or null, +=
+    int Mo, N, Kb;
+};
+// One launch of a plan: problems [first, first + count) of the list,
+// their splits and block counts.  count == 1 is a plain ss_wgrad_tn
+// call (split 0 there = that launcher's own choice, blocks = its grid).
+struct WgradGroupLaunch {
+    int first, count;
+    int split[SS_WGRAD_GROUP_MAX];
+    int blocks[SS_WGRAD_GROUP_MAX];
+};
+// Plans the launches of a list from its shapes alone (pointers are not
+// read): maximal runs of consecutive problems with the same tile
+// configuration, at most SS_WGRAD_GROUP_MAX each.  splits: per problem,
+// 0 (the group rule) or >= 2; null = all 0.  Writes at most n entries
+// to `out`; returns their number, or -1 for a bad shape or split.
+int ss_wgrad_group_plan(const WgradProblem* problems, int n,
+                        const int* splits, WgradGroupLaunch* out);
+// Runs the plan: a run of two or more is ONE wgrad_group_kernel launch,
+// a run of one goes through ss_wgrad_tn.  False, with nothing launched,
+// for a bad shape, split or pointer.
+bool ss_wgrad_tn_group(const WgradProblem* problems, int n,
+                       const int* splits, hipStream_t stream);
+
 // ---- head.hip
 bool ss_head_fwd_fused(const void* x, const void* W, const void* bias,
                        void* probs, int M, int K, int C, int rows_per_block,

@@ -3,11 +3,18 @@ one LDS staging set against two (wgrad_tn's `stages` argument), over the
 split sweep of profiles/r03_wgrad_onchip_reduce.md §2.
 
     python scripts/microbench_wgrad_group.py [--rounds 5] [--iters 200]
+        [--only all|stages|group] [--cells "6,16;7,8"]
 
 Each (shape, split) cell times both depths alternately, `rounds` times
 each, and prints the min / median / max of the per-call time in µs, so a
-difference can be read against the cell's own spread.  The last block
+difference can be read against the cell's own spread.  The next block
 times the four launches of one flagship step back to back.
+
+The last block (alone with --only group) is the grouped launch
+(wgrad_tn_group): the head and the two hidden layers of a step, each
+with operands and gradients of its own, in ONE launch, over hidden split
+x head split x head first / last in the grid, each cell against the
+three launches back to back at the launcher's splits.
 """
 import argparse
 import statistics
@@ -22,6 +29,10 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--rounds", type=int, default=5)
 ap.add_argument("--iters", type=int, default=200)
 ap.add_argument("--batch", type=int, default=16384)
+ap.add_argument("--only", choices=["all", "stages", "group"], default="all")
+ap.add_argument("--cells", default="",
+                help="grouped launch: 'hidden,head;...' split pairs to time "
+                     "instead of the full sweep")
 args = ap.parse_args()
 
 e = load_ext(required=True)
@@ -70,9 +81,11 @@ for Mo, N in layers:
 
 print(f"wgrad_tn unmasked, Kb = {Kb}; µs per call as min / median / max "
       f"of {args.rounds} rounds x {args.iters} calls")
-print("| Mo x N | split | stages 1 | stages 2 |")
-print("|---|---:|---|---|")
-for (Mo, N), (dy, x, gw, gb) in zip(layers, ops):
+if args.only != "group":
+    print("| Mo x N | split | stages 1 | stages 2 |")
+    print("|---|---:|---|---|")
+for (Mo, N), (dy, x, gw, gb) in zip(layers if args.only != "group" else [],
+                                    ops):
     for sk in (0, 8, 16, 32, 64):
         r = cell({
             s: (lambda s=s: e.wgrad_tn(dy, x, gw, gb, empty, sk, s))
@@ -88,13 +101,59 @@ def step(stages):
         e.wgrad_tn(dy, x, gw, gb, empty, 0, stages)
 
 
-print("\nthe four wgrads of one step, auto split, back to back")
-print("| arm | µs per step (min / median / max) |")
-print("|---|---|")
-arms = {
-    "stages 1 everywhere": lambda: step(1),
-    "stages 2 everywhere": lambda: step(2),
-    "launcher's choice": lambda: step(0),
-}
-for k, v in cell(arms).items():
-    print(f"| {k} | {fmt(v)} |")
+if args.only != "group":
+    print("\nthe four wgrads of one step, auto split, back to back")
+    print("| arm | µs per step (min / median / max) |")
+    print("|---|---|")
+    arms = {
+        "stages 1 everywhere": lambda: step(1),
+        "stages 2 everywhere": lambda: step(2),
+        "launcher's choice": lambda: step(0),
+    }
+    for k, v in cell(arms).items():
+        print(f"| {k} | {fmt(v)} |")
+
+if args.only == "stages":
+    sys.exit(0)
+
+
+# ---- grouped launch: head + two hidden layers, separate buffers each
+def problem(Mo, N, seed):
+    g = torch.Generator().manual_seed(seed)
+    return (torch.randn(Kb, Mo, generator=g).to(dev).bfloat16(),
+            torch.randn(Kb, N, generator=g).to(dev).bfloat16(),
+            torch.zeros(Mo, N, device=dev), torch.zeros(Mo, device=dev))
+
+
+head, hid3, hid2 = problem(10, 256, 1), problem(256, 256, 2), \
+    problem(256, 256, 3)
+
+
+def three_launches():
+    for dy, x, gw, gb in (head, hid3, hid2):
+        e.wgrad_tn(dy, x, gw, gb, empty, 0, 0)
+
+
+shapes = [(Kb, 10, 256), (Kb, 256, 256), (Kb, 256, 256)]
+rule = e.wgrad_group_plan(shapes, None)
+print(f"\nhead + 2 hidden wgrads, own buffers each; the group rule plans "
+      f"{rule}")
+print("| hidden split | head split | head | blocks | three launches | "
+      "one grouped launch |")
+print("|---:|---:|---|---:|---|---|")
+sweep = [(hs, ks) for hs in (0, 4, 6, 8, 12, 16)
+         for ks in ((0,) if hs == 0 else (8, 16, 32, 64))]
+if args.cells:
+    sweep = [tuple(int(v) for v in c.split(",")) for c in args.cells.split(";")]
+for hs, ks in sweep:  # 0, 0 = the launcher's rule
+    for first in (True, False):
+        probs = [head, hid3, hid2] if first else [hid3, hid2, head]
+        splits = [ks, hs, hs] if first else [hs, hs, ks]
+        sh = shapes if first else shapes[1:] + shapes[:1]
+        blocks = sum(e.wgrad_group_plan(sh, splits)[0][2])
+        r = cell({
+            "three": three_launches,
+            "group": lambda: e.wgrad_tn_group(probs, splits),
+        })
+        print(f"| {hs} | {ks} | {'first' if first else 'last'} | "
+              f"{blocks} | {fmt(r['three'])} | {fmt(r['group'])} |")

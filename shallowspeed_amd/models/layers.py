@@ -824,9 +824,11 @@ class Sequential(Module):
 
     def _backward_chain(self, plan, lin, head, target, mubatch_id):
         """Backward of the head pair and the planned ReLU layers through
-        ONE F.bwd_chain launch, then one unmasked wgrad per layer in the
-        per-layer order (head, then top to bottom), grad hooks fired
-        after each.  Returns (True, dx of the lowest planned layer), or
+        ONE F.bwd_chain launch, then the unmasked wgrads in the
+        per-layer order (head, then top to bottom): through one grouped
+        call (_wgrad_group), or one launch per layer in deterministic
+        mode, under deferred wgrad and with F.set_wgrad_group(False);
+        grad hooks fire after the launch that holds the layer.  Returns (True, dx of the lowest planned layer), or
         (False, None) with no stash touched when the tensors do not meet
         the kernel's contract."""
         s = head._cache.get(("s", mubatch_id))
@@ -853,9 +855,15 @@ class Sequential(Module):
             F.head_metrics(s, target, head._metrics, head.kind)
         head._unstash("s", mubatch_id)
         lin._unstash("x", mubatch_id)
-        self._wgrad_of(lin, dz_head, x)
-        self._fire_grad_hooks(head)
-        self._fire_grad_hooks(lin)
+        # deterministic mode keeps the single-owner kernel per layer,
+        # deferred wgrad keeps its chunks for the flush
+        grouped = F.wgrad_group_enabled() and not F.deterministic() \
+            and not any(l._defer_wgrad for l in [lin] + chain)
+        items = [(lin, dz_head, x, (head, lin))]
+        if not grouped:
+            self._wgrad_of(lin, dz_head, x)
+            self._fire_grad_hooks(head)
+            self._fire_grad_hooks(lin)
         for layer, (i, dg), dz in zip(chain, plan, dzs):
             xl = layer._unstash("x", mubatch_id)
             layer._unstash("y", mubatch_id)
@@ -864,9 +872,38 @@ class Sequential(Module):
                 # needed (in_dims != 256): the ordinary unmasked dgrad
                 dx = F.linear_dgrad(dz, layer.weight.compute(),
                                     layer.weight.compute_t())
+            if grouped:
+                items.append((layer, dz, xl, (layer,)))
+                continue
             self._wgrad_of(layer, dz, xl)
             self._fire_grad_hooks(layer)
+        if grouped:
+            self._wgrad_group(items)
         return True, dx
+
+    def _wgrad_group(self, items):
+        """Weight gradients of `items`, (layer, dz, x, layers whose grad
+        hooks follow), through F.linear_wgrad_group: same-tile layers
+        share a launch.  Without grad hooks that is one call.  With
+        hooks the list is cut at the launch boundaries and a layer's
+        hooks fire right after the launch that holds its gradient, in
+        the per-layer order, so a later launch (the first layer's) is
+        issued after the hooks of the layers before it and no bucket
+        waits on a wgrad it does not need."""
+        probs = [(dz, x, l.weight.grad, l.bias.grad) for l, dz, x, _ in items]
+        if not self._grad_hooks:
+            cuts = [list(range(len(items)))]
+        elif probs[0][0].is_cuda:
+            cuts = [la["problems"] for la in F.wgrad_group_plan(
+                [(dz.shape[0], dz.shape[1], x.shape[1])
+                 for dz, x, _, _ in probs])]
+        else:
+            cuts = [[k] for k in range(len(items))]
+        for cut in cuts:
+            F.linear_wgrad_group([probs[k] for k in cut])
+            for k in cut:
+                for hl in items[k][3]:
+                    self._fire_grad_hooks(hl)
 
     def backward(self, dout, mubatch_id: int = 0):
         self._settle_zero_grad()

@@ -322,6 +322,58 @@ def linear_wgrad_acc(dy, x, grad_w, grad_b=None, mask_src=None, split_k=0):
         grad_b += dy.sum(dim=0).to(grad_b.dtype)
 
 
+_WGRAD_GROUP = None
+
+
+def set_wgrad_group(flag: bool):
+    """Issue the unmasked weight gradients that follow the backward
+    chain through one linear_wgrad_group call, so that same-tile layers
+    (the flagship's head and hidden layers) share a launch.  Off, each
+    layer is its own launch.  Gradients differ in f32 atomic arrival
+    order only.  SS_WGRAD_GROUP=0 (read once) turns it off."""
+    global _WGRAD_GROUP
+    _WGRAD_GROUP = bool(flag)
+
+
+def wgrad_group_enabled() -> bool:
+    global _WGRAD_GROUP
+    if _WGRAD_GROUP is None:
+        import os
+
+        _WGRAD_GROUP = os.environ.get("SS_WGRAD_GROUP", "1") != "0"
+    return _WGRAD_GROUP
+
+
+def wgrad_group_plan(shapes, splits=None):
+    """The launches linear_wgrad_group makes on the GPU for problems of
+    these (Kb, Mo, N) shapes: a list, in launch order, of
+    {"problems": indices into `shapes`, "splits": ..., "blocks": ...}.
+    A launch of one problem is a plain wgrad_tn call.  Host-side only,
+    but needs the built extension."""
+    ext = load_ext(required=True)
+    return [dict(problems=list(i), splits=list(s), blocks=list(b))
+            for i, s, b in ext.wgrad_group_plan(
+                [tuple(int(v) for v in sh) for sh in shapes],
+                None if splits is None else [int(s) for s in splits])]
+
+
+def linear_wgrad_group(problems, splits=None):
+    """linear_wgrad_acc (unmasked) for each (dy, x, grad_w, grad_b) of
+    `problems`, grad_b may be None.  On the GPU consecutive problems of
+    one tile configuration run side by side in one launch; splits is
+    None or one value per problem, 0 (the launcher's rule) or >= 2."""
+    problems = list(problems)
+    if not problems:
+        return
+    if _is_gpu(problems[0][0]):
+        load_ext(required=True).wgrad_tn_group(
+            [tuple(p) for p in problems],
+            None if splits is None else [int(s) for s in splits])
+        return
+    for dy, x, gw, gb in problems:
+        linear_wgrad_acc(dy, x, gw, gb)
+
+
 # ---------------------------------------------------------------- relu
 
 def relu_fwd(x):
