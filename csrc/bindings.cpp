@@ -571,6 +571,42 @@ std::vector<torch::Tensor> head_bwd_fused(torch::Tensor probs,
     return {dz, dx};
 }
 
+namespace {
+
+// hs / w_ts of a backward chain launch, top layer first: every h is a
+// plain [M][H], every W^T a plain [H][H]; their pointers go to hp / wp.
+bool bwd_chain_operands(const std::vector<torch::Tensor>& hs,
+                        const std::vector<torch::Tensor>& w_ts, int64_t M,
+                        int64_t H, const void** hp, const void** wp) {
+    for (size_t l = 0; l < hs.size(); ++l) {
+        if (!plain(hs[l], 2) || hs[l].size(0) != M || hs[l].size(1) != H)
+            return false;
+        hp[l] = hs[l].data_ptr();
+        if (l < w_ts.size()) {
+            if (!plain(w_ts[l], 2) || w_ts[l].size(0) != H ||
+                w_ts[l].size(1) != H)
+                return false;
+            wp[l] = w_ts[l].data_ptr();
+        }
+    }
+    return true;
+}
+
+// Appends dz_0 .. dz_{n-1} (pointers to dp) and, when want_dx, dx to
+// out; returns dx's pointer or null.
+void* bwd_chain_outputs(const std::vector<torch::Tensor>& hs, bool want_dx,
+                        std::vector<torch::Tensor>& out, void** dp) {
+    for (size_t l = 0; l < hs.size(); ++l) {
+        out.push_back(torch::empty_like(hs[l]));
+        dp[l] = out.back().data_ptr();
+    }
+    if (!want_dx) return nullptr;
+    out.push_back(torch::empty_like(hs.back()));
+    return out.back().data_ptr();
+}
+
+}  // namespace
+
 // Backward chain (bwd_chain.hip): head backward and the 256-wide ReLU
 // layers' data gradients below it in one launch.  hs[l] / w_ts[l], top
 // layer first: the layer's post-ReLU output and its W^T; w_ts holds one
@@ -597,33 +633,51 @@ std::vector<torch::Tensor> bwd_chain(torch::Tensor probs, torch::Tensor target,
     const void* hp[SS_BWD_CHAIN_MAX] = {};
     const void* wp[SS_BWD_CHAIN_MAX] = {};
     void* dp[SS_BWD_CHAIN_MAX] = {};
-    for (int64_t l = 0; l < n; ++l) {
-        if (!plain(hs[l], 2) || hs[l].size(0) != M || hs[l].size(1) != H)
-            return {};
-        hp[l] = hs[l].data_ptr();
-        if (l < nw) {
-            if (!plain(w_ts[l], 2) || w_ts[l].size(0) != H ||
-                w_ts[l].size(1) != H)
-                return {};
-            wp[l] = w_ts[l].data_ptr();
-        }
-    }
+    if (!bwd_chain_operands(hs, w_ts, M, H, hp, wp)) return {};
     std::vector<torch::Tensor> out;
     out.push_back(torch::empty_like(probs));
-    for (int64_t l = 0; l < n; ++l) {
-        out.push_back(torch::empty_like(hs[l]));
-        dp[l] = out.back().data_ptr();
-    }
-    void* dx_p = nullptr;
-    if (nw == n) {
-        out.push_back(torch::empty_like(hs[n - 1]));
-        dx_p = out.back().data_ptr();
-    }
+    void* dx_p = bwd_chain_outputs(hs, nw == n, out, dp);
     if (!ss_bwd_chain(probs.data_ptr(), target.data_ptr(),
                       w_head_t.data_ptr(), out[0].data_ptr(), hp, wp, dp,
                       (int)n, dx_p, (int)M, (int)H, (int)C,
                       (float)(1.0 / global_batch), (int)rows, (int)waves,
                       (int)w_lds, (float)dz_scale, cur_stream()))
+        return {};
+    return out;
+}
+
+// Stage arm of the backward chain, for a pipeline stage with no head:
+// the chain starts from dout [M][256], the gradient of the top layer's
+// output.  hs / w_ts as bwd_chain.  Returns [dz_0, ..., dz_{n-1}(, dx)],
+// or an EMPTY list with nothing allocated or launched.
+std::vector<torch::Tensor> bwd_chain_stage(torch::Tensor dout,
+                                           std::vector<torch::Tensor> hs,
+                                           std::vector<torch::Tensor> w_ts,
+                                           int64_t rows, int64_t waves,
+                                           int64_t w_lds, double dz_scale) {
+    constexpr int64_t H = 256;
+    const int64_t n = (int64_t)hs.size();
+    const int64_t nw = (int64_t)w_ts.size();
+    if (n < 1 || n > SS_BWD_CHAIN_MAX || (nw != n && nw != n - 1)) return {};
+    if (!plain(dout, 2) || dout.size(1) != H) return {};
+    const int64_t M = dout.size(0);
+    if (M > INT_MAX / 512) return {};
+    // the arms the launcher is built for, refused before anything is
+    // allocated
+    if ((rows != 0 && rows != 32 && rows != 64) ||
+        (waves != 0 && waves != 4 && waves != 8))
+        return {};
+    if ((float)dz_scale != 1.f && (waves == 4 || w_lds != 0)) return {};
+    if (w_lds == 1 && ((rows != 0 && rows != 64) || waves == 4)) return {};
+    const void* hp[SS_BWD_CHAIN_MAX] = {};
+    const void* wp[SS_BWD_CHAIN_MAX] = {};
+    void* dp[SS_BWD_CHAIN_MAX] = {};
+    if (!bwd_chain_operands(hs, w_ts, M, H, hp, wp)) return {};
+    std::vector<torch::Tensor> out;
+    void* dx_p = bwd_chain_outputs(hs, nw == n, out, dp);
+    if (!ss_bwd_chain_stage(dout.data_ptr(), hp, wp, dp, (int)n, dx_p, (int)M,
+                            (int)H, (int)rows, (int)waves, (int)w_lds,
+                            (float)dz_scale, cur_stream()))
         return {};
     return out;
 }
@@ -637,14 +691,13 @@ std::vector<torch::Tensor> bwd_chain(torch::Tensor probs, torch::Tensor target,
 // path.  zero: a contiguous f32 tensor on x's device that the launch
 // also fills with zeros (the step's flat gradient buffer), or None; it
 // is left untouched when the launch is refused.
-std::vector<torch::Tensor> fwd_chain(torch::Tensor x,
-                                     std::vector<torch::Tensor> ws,
-                                     std::vector<torch::Tensor> bs,
-                                     torch::Tensor w_head,
-                                     torch::Tensor b_head, int64_t rows,
-                                     int64_t waves, int64_t l1,
-                                     int64_t kloop,
-                                     std::optional<torch::Tensor> zero) {
+// head == false is the stage arm (fwd_chain_stage below): no w_head /
+// b_head / zero, and no probs in the result.
+static std::vector<torch::Tensor> fwd_chain_any(
+    bool head, const torch::Tensor& x, const std::vector<torch::Tensor>& ws,
+    const std::vector<torch::Tensor>& bs, const torch::Tensor& w_head,
+    const torch::Tensor& b_head, int64_t rows, int64_t waves, int64_t l1,
+    int64_t kloop, const std::optional<torch::Tensor>& zero) {
     constexpr int64_t H = 256;
     const int64_t n = (int64_t)ws.size();
     if (n < 1 || n > SS_FWD_CHAIN_MAX || (int64_t)bs.size() != n) return {};
@@ -658,10 +711,12 @@ std::vector<torch::Tensor> fwd_chain(torch::Tensor x,
         zero_p = zero->data_ptr();
         zero_bytes = zero->numel() * 4;
     }
-    if (!plain(x, 2) || !plain(w_head, 2) || !plain(b_head, 1)) return {};
-    const int64_t M = x.size(0), K0 = x.size(1), C = w_head.size(0);
+    if (!plain(x, 2)) return {};
+    if (head && (!plain(w_head, 2) || !plain(b_head, 1))) return {};
+    const int64_t M = x.size(0), K0 = x.size(1);
+    const int64_t C = head ? w_head.size(0) : 1;
     if (M > INT_MAX / 1024 || K0 % 8 != 0 || C > 16 ||
-        w_head.size(1) != H || b_head.numel() != C)
+        (head && (w_head.size(1) != H || b_head.numel() != C)))
         return {};
     if ((rows != 0 && rows != 32 && rows != 64) ||
         (waves != 0 && waves != 4 && waves != 8) || l1 < 0 || l1 > 2 ||
@@ -682,6 +737,13 @@ std::vector<torch::Tensor> fwd_chain(torch::Tensor x,
         out.push_back(torch::empty({M, H}, x.options()));
         hp[l] = out.back().data_ptr();
     }
+    if (!head) {
+        if (!ss_fwd_chain_stage(x.data_ptr(), wp, bp, hp, (int)n, (int)M,
+                                (int)K0, (int)H, (int)rows, (int)waves,
+                                (int)l1, (int)kloop, cur_stream()))
+            return {};
+        return out;
+    }
     out.push_back(torch::empty({M, C}, x.options()));
     if (!ss_fwd_chain(x.data_ptr(), wp, bp, hp, (int)n, w_head.data_ptr(),
                       b_head.data_ptr(), out.back().data_ptr(), (int)M,
@@ -689,6 +751,30 @@ std::vector<torch::Tensor> fwd_chain(torch::Tensor x,
                       (int)kloop, zero_p, (long)zero_bytes, cur_stream()))
         return {};
     return out;
+}
+
+std::vector<torch::Tensor> fwd_chain(torch::Tensor x,
+                                     std::vector<torch::Tensor> ws,
+                                     std::vector<torch::Tensor> bs,
+                                     torch::Tensor w_head,
+                                     torch::Tensor b_head, int64_t rows,
+                                     int64_t waves, int64_t l1,
+                                     int64_t kloop,
+                                     std::optional<torch::Tensor> zero) {
+    return fwd_chain_any(true, x, ws, bs, w_head, b_head, rows, waves, l1,
+                         kloop, zero);
+}
+
+// Stage arm of the forward chain, for a pipeline stage with no head:
+// returns [h_0, ..., h_{n-1}], or an EMPTY list with nothing allocated
+// or launched.
+std::vector<torch::Tensor> fwd_chain_stage(torch::Tensor x,
+                                           std::vector<torch::Tensor> ws,
+                                           std::vector<torch::Tensor> bs,
+                                           int64_t rows, int64_t waves,
+                                           int64_t l1, int64_t kloop) {
+    return fwd_chain_any(false, x, ws, bs, x, x, rows, waves, l1, kloop,
+                         std::nullopt);
 }
 
 // Adds the metric totals of (probs, target) into acc: loss_sum (kind
@@ -930,6 +1016,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           py::arg("b_head"), py::arg("rows") = 0, py::arg("waves") = 0,
           py::arg("l1") = 0, py::arg("kloop") = 0,
           py::arg("zero") = py::none());
+    m.def("fwd_chain_stage", &fwd_chain_stage,
+          "256-wide ReLU layers of a headless pipeline stage in one launch "
+          "-> [h_l...], or [] outside the contract",
+          py::arg("x"), py::arg("ws"), py::arg("bs"), py::arg("rows") = 0,
+          py::arg("waves") = 0, py::arg("l1") = 0, py::arg("kloop") = 0);
+    m.def("bwd_chain_stage", &bwd_chain_stage,
+          "256-wide ReLU dgrads of a headless pipeline stage from dout in "
+          "one launch -> [dz_l..., (dx)], or [] outside the contract",
+          py::arg("dout"), py::arg("hs"), py::arg("w_ts"),
+          py::arg("rows") = 0, py::arg("waves") = 0, py::arg("w_lds") = 0,
+          py::arg("dz_scale") = 1.0);
     m.def("head_metrics", &head_metrics,
           "metric totals of (probs, target) into a slotted accumulator",
           py::arg("probs"), py::arg("target"), py::arg("acc"),

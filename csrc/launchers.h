@@ -113,7 +113,7 @@ bool ss_head_bwd_fused(const void* probs, const void* target, const void* x,
 bool ss_head_metrics(const void* probs, const void* target, void* acc,
                      int slots, int M, int C, int kind, hipStream_t stream);
 
-// ---- bwd_chain.hip
+// ---- bwd_chain.hip / bwd_chain_stage.hip
 // h / wt / dz: nlayers pointers each, top layer first (post-ReLU output,
 // W^T or null where the chain ends, masked gradient out).  dz_scale
 // (inverted dropout's 1/keep) scales every dz_l: 1.f is the unscaled
@@ -125,8 +125,17 @@ bool ss_bwd_chain(const void* probs, const void* target, const void* Wt_head,
                   void* const* dz, int nlayers, void* dx, int M, int H, int C,
                   float inv_gb, int rows, int waves, int w_lds,
                   float dz_scale, hipStream_t stream);
+// The stage arm, for a pipeline stage with no head: the chain starts
+// from dout [M][256], the received gradient of the top layer's output,
+// 16-byte aligned.  Everything else as ss_bwd_chain, except that the
+// shipped rows are 32 where 64-row tiles would cover at most half of the
+// CUs, and the scaled form is built for both eight-wave arms.
+bool ss_bwd_chain_stage(const void* dout, const void* const* h,
+                        const void* const* wt, void* const* dz, int nlayers,
+                        void* dx, int M, int H, int rows, int waves,
+                        int w_lds, float dz_scale, hipStream_t stream);
 
-// ---- fwd_chain.hip
+// ---- fwd_chain.hip / fwd_chain_stage.hip
 // w / b / h: nlayers pointers each, bottom layer first (W [256][in],
 // bias, post-ReLU output).  x is the input of layer 0, [M][K0]; l1
 // selects how the chain starts (0 = shipped choice, 1 = from a stored
@@ -142,6 +151,12 @@ bool ss_fwd_chain(const void* x, const void* const* w, const void* const* b,
                   const void* b_head, void* probs, int M, int K0, int H, int C,
                   int rows, int waves, int l1, int kloop, void* zero_ptr,
                   long zero_bytes, hipStream_t stream);
+// The stage arm, for a pipeline stage with no head: the launch ends with
+// h of the top layer.  Same contract, arms and shipped choices.
+bool ss_fwd_chain_stage(const void* x, const void* const* w,
+                        const void* const* b, void* const* h, int nlayers,
+                        int M, int K0, int H, int rows, int waves, int l1,
+                        int kloop, hipStream_t stream);
 
 // ---- fused_mlp.hip
 bool ss_fused_mlp_fwd(const void* x, const void* desc, int M, int in_dim,

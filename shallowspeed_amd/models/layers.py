@@ -626,12 +626,15 @@ class Sequential(Module):
             return None
         return pair
 
-    def _chain_run(self):
+    def _chain_run(self, top=None):
         """Indices, top first, of the consecutive Linear(activation=
-        "relu") layers with out_dims == 256 right under the head pair,
-        at most _CHAIN_MAX_LAYERS.  A chain plan is a prefix of it."""
+        "relu") layers with out_dims == 256 from layer `top` down
+        (default: right under the head pair), at most
+        _CHAIN_MAX_LAYERS.  A chain plan is a prefix of it."""
         run = []
-        for i in range(len(self.layers) - 3, -1, -1):
+        if top is None:
+            top = len(self.layers) - 3
+        for i in range(top, -1, -1):
             layer = self.layers[i]
             if len(run) == self._CHAIN_MAX_LAYERS \
                     or type(layer) is not Linear \
@@ -641,7 +644,7 @@ class Sequential(Module):
             run.append(i)
         return run
 
-    def _fwd_chain_plan(self):
+    def _fwd_chain_plan(self, top=None):
         """Which layers the forward chain kernel (F.fwd_chain) takes
         together with the head: their indices, bottom first, or None
         when the head or the layers under it do not qualify.
@@ -652,12 +655,15 @@ class Sequential(Module):
         in the chain when in_dims == 256, or, with F.fwd_chain_l1(),
         when it ends the run and in_dims % 8 == 0.  No chain with
         dropout or an fp8 forward on a layer it would take.  Looks at
-        the layer configuration only — no tensors, no device."""
-        if not F.fwd_chain_enabled() or not F.head_fused() \
-                or self._chain_head_pair() is None:
+        the layer configuration only — no tensors, no device.
+
+        top (for _fwd_stage_plan): the run starts at that layer and no
+        head is asked for."""
+        if not F.fwd_chain_enabled() or top is None and (
+                not F.head_fused() or self._chain_head_pair() is None):
             return None
         plan = []
-        for i in self._chain_run():
+        for i in self._chain_run(top):
             layer = self.layers[i]
             streamed = layer.in_dims != self._CHAIN_WIDTH
             if streamed and not (F.fwd_chain_l1() and layer.in_dims >= 8
@@ -670,14 +676,37 @@ class Sequential(Module):
                 break
         return plan[::-1] or None
 
+    def _fwd_stage_plan(self):
+        """_fwd_chain_plan for a stage with no head pair (every pipeline
+        stage but the last): the layers the stage arm of the forward
+        chain (F.fwd_chain_stage) takes, by the same rules, when the run
+        of 256-wide ReLU Linears ends at the stage's last layer.  None
+        whenever there is a head pair: the headed plan owns that stage."""
+        if self._head_pair() is not None:
+            return None
+        return self._fwd_chain_plan(top=len(self.layers) - 1)
+
     def _forward_chain(self, plan, lin, head, x, mubatch_id):
         """Forward of the planned ReLU layers and the head pair through
         ONE F.fwd_chain launch, leaving the stashes the layers' own
         forwards leave.  Returns probs, or None with no stash touched
-        when the tensors do not meet the kernel's contract."""
+        when the tensors do not meet the kernel's contract.  lin = head
+        = None (a stage plan): ONE F.fwd_chain_stage launch, which never
+        takes a deferred zero_grad along; returns the top layer's
+        output."""
+        chain = [self.layers[i] for i in plan]
+        if lin is None:
+            hs = F.fwd_chain_stage(x, [l.weight.compute() for l in chain],
+                                   [l.bias.compute() for l in chain])
+            if hs is None:
+                return None
+            for layer, h in zip(chain, hs):
+                layer._stash("x", mubatch_id, x)
+                layer._stash("y", mubatch_id, h)
+                x = h
+            return x
         if not F.head_fused_ok(x, lin):
             return None
-        chain = [self.layers[i] for i in plan]
         # a deferred zero_grad rides in this launch (same stream, ahead
         # of every kernel that adds to the gradients)
         zero = self._flat_grad if getattr(self, "_zero_pending", False) \
@@ -703,12 +732,18 @@ class Sequential(Module):
         x = inputs
         pair = self._head_pair()
         n_plain = len(self.layers) - 2 if pair else len(self.layers)
-        plan = self._fwd_chain_plan() if pair and inputs.is_cuda else None
+        plan = None
+        if inputs.is_cuda:
+            plan = self._fwd_chain_plan() if pair else self._fwd_stage_plan()
         if plan:
+            if not pair:
+                # the stage launch takes no deferred zero_grad along
+                self._settle_zero_grad()
             # layers below the chain run their own forward first
             for layer in self.layers[:plan[0]]:
                 x = layer.forward(x, mubatch_id)
-            s = self._forward_chain(plan, pair[0], pair[1], x, mubatch_id)
+            s = self._forward_chain(plan, *(pair or (None, None)), x,
+                                    mubatch_id)
             if s is not None:
                 return s
             first = plan[0]
@@ -777,7 +812,7 @@ class Sequential(Module):
         self._fire_grad_hooks(lin)
         return dx
 
-    def _bwd_chain_plan(self, mubatch_rows: int = 1):
+    def _bwd_chain_plan(self, mubatch_rows: int = 1, top=None):
         """Which layers the backward chain kernel (F.bwd_chain) takes:
         a list of (layer index, dgrad_in_chain), top layer first, or
         None when the head or the layers under it do not qualify.
@@ -789,13 +824,17 @@ class Sequential(Module):
         with the first layer whose dgrad is not (that layer still gets
         its dz from the kernel), or above the first layer that is no
         such Linear.  Looks at the layer configuration only — no
-        tensors, no device."""
+        tensors, no device.
+
+        top (for _bwd_stage_plan): the run starts at that layer and no
+        head is asked for."""
         if mubatch_rows < 1 or not F.bwd_chain_enabled() \
-                or not F.head_fused() or F.head_wgrad_fused() \
-                or self._chain_head_pair() is None:
+                or top is None and (
+                    not F.head_fused() or F.head_wgrad_fused()
+                    or self._chain_head_pair() is None):
             return None
         plan = []
-        for i in self._chain_run():
+        for i in self._chain_run(top):
             layer = self.layers[i]
             need_dx = not (i == 0 and self._skip_input_grad)
             in_chain = need_dx and layer.in_dims == self._CHAIN_WIDTH
@@ -811,6 +850,16 @@ class Sequential(Module):
                 len({self.layers[i].dz_scale() for i, _ in plan}) > 1:
             return None
         return plan or None
+
+    def _bwd_stage_plan(self, mubatch_rows: int = 1):
+        """_bwd_chain_plan for a stage with no head pair: the layers the
+        stage arm of the backward chain (F.bwd_chain_stage) takes from
+        the received gradient, by the same rules, when the run of
+        256-wide ReLU Linears ends at the stage's last layer.  None
+        whenever there is a head pair."""
+        if self._head_pair() is not None:
+            return None
+        return self._bwd_chain_plan(mubatch_rows, top=len(self.layers) - 1)
 
     def _wgrad_of(self, layer, dz, x):
         """Unmasked weight gradient of `layer` from its dz: now, or kept
@@ -828,39 +877,57 @@ class Sequential(Module):
         per-layer order (head, then top to bottom): through one grouped
         call (_wgrad_group), or one launch per layer in deterministic
         mode, under deferred wgrad and with F.set_wgrad_group(False);
-        grad hooks fire after the launch that holds the layer.  Returns (True, dx of the lowest planned layer), or
-        (False, None) with no stash touched when the tensors do not meet
-        the kernel's contract."""
-        s = head._cache.get(("s", mubatch_id))
-        x = lin._cache.get(("x", mubatch_id))
+        grad hooks fire after the launch that holds the layer.  Returns
+        (True, dx of the lowest planned layer), or (False, None) with no
+        stash touched when the tensors do not meet the kernel's contract.
+
+        lin = head = None (a stage plan): `target` is the gradient the
+        stage received, and the launch is ONE F.bwd_chain_stage on it;
+        the wgrads follow in the same way."""
         chain = [self.layers[i] for i, _ in plan]
         hs = [l._cache.get(("y", mubatch_id)) for l in chain]
-        if s is None or x is None or any(h is None for h in hs) \
-                or not F.head_fused_ok(x, lin):
-            return False, None
-        if target.dtype != s.dtype:
-            target = target.to(s.dtype)
-        if not target.is_contiguous():
-            target = target.contiguous()
-        w_ts = [l.weight.compute_t() for l, (_, dg) in zip(chain, plan) if dg]
-        res = F.bwd_chain(s, target, lin.weight.compute_t(),
-                          head.global_batch_size, hs, w_ts,
-                          dz_scale=chain[0].dz_scale())
-        if res is None:
-            return False, None
-        dz_head, dzs, dx = res
-        # the chain kernel does not count: the standalone metrics launch
-        # reads the same probs / target (only when metrics are on)
-        if head._metrics is not None and head._training:
-            F.head_metrics(s, target, head._metrics, head.kind)
-        head._unstash("s", mubatch_id)
-        lin._unstash("x", mubatch_id)
+        if lin is None:
+            if any(h is None for h in hs):
+                return False, None
+            res = F.bwd_chain_stage(
+                target, hs, [l.weight.compute_t()
+                             for l, (_, dg) in zip(chain, plan) if dg],
+                dz_scale=chain[0].dz_scale())
+            if res is None:
+                return False, None
+            dzs, dx = res
+            heads, items = [], []
+        else:
+            s = head._cache.get(("s", mubatch_id))
+            x = lin._cache.get(("x", mubatch_id))
+            if s is None or x is None or any(h is None for h in hs) \
+                    or not F.head_fused_ok(x, lin):
+                return False, None
+            if target.dtype != s.dtype:
+                target = target.to(s.dtype)
+            if not target.is_contiguous():
+                target = target.contiguous()
+            w_ts = [l.weight.compute_t()
+                    for l, (_, dg) in zip(chain, plan) if dg]
+            res = F.bwd_chain(s, target, lin.weight.compute_t(),
+                              head.global_batch_size, hs, w_ts,
+                              dz_scale=chain[0].dz_scale())
+            if res is None:
+                return False, None
+            dz_head, dzs, dx = res
+            # the chain kernel does not count: the standalone metrics
+            # launch reads the same probs / target (only when metrics
+            # are on)
+            if head._metrics is not None and head._training:
+                F.head_metrics(s, target, head._metrics, head.kind)
+            head._unstash("s", mubatch_id)
+            lin._unstash("x", mubatch_id)
+            heads, items = [lin], [(lin, dz_head, x, (head, lin))]
         # deterministic mode keeps the single-owner kernel per layer,
         # deferred wgrad keeps its chunks for the flush
         grouped = F.wgrad_group_enabled() and not F.deterministic() \
-            and not any(l._defer_wgrad for l in [lin] + chain)
-        items = [(lin, dz_head, x, (head, lin))]
-        if not grouped:
+            and not any(l._defer_wgrad for l in heads + chain)
+        if items and not grouped:
             self._wgrad_of(lin, dz_head, x)
             self._fire_grad_hooks(head)
             self._fire_grad_hooks(lin)
@@ -910,10 +977,12 @@ class Sequential(Module):
         d = dout
         last = len(self.layers) - 1
         pair = self._head_pair()
-        plan = self._bwd_chain_plan(dout.shape[0]) \
-            if pair and dout.is_cuda else None
+        plan = None
+        if dout.is_cuda:
+            plan = self._bwd_chain_plan(dout.shape[0]) if pair \
+                else self._bwd_stage_plan(dout.shape[0])
         if plan:
-            ok, dx = self._backward_chain(plan, pair[0], pair[1], d,
+            ok, dx = self._backward_chain(plan, *(pair or (None, None)), d,
                                           mubatch_id)
             if ok:
                 d = dx

@@ -100,8 +100,10 @@ def set_bwd_chain(flag: bool):
     """Run the head backward and the 256-wide ReLU layers' data
     gradients below it as the one kernel of csrc/bwd_chain.hip (see
     bwd_chain).  Every dz and dx keeps its bits; the weight gradients
-    then run unmasked on dz.  Default on; SS_BWD_CHAIN=0 (read once)
-    turns it off."""
+    then run unmasked on dz.  A pipeline stage with no head runs its
+    layers' data gradients as that kernel's stage arm, from the received
+    gradient (see bwd_chain_stage).  Default on; SS_BWD_CHAIN=0 (read
+    once) turns both off."""
     global _BWD_CHAIN
     _BWD_CHAIN = bool(flag)
 
@@ -138,8 +140,9 @@ _FWD_CHAIN = None
 def set_fwd_chain(flag: bool):
     """Run the 256-wide ReLU layers under the fused head and the head
     forward as the one kernel of csrc/fwd_chain.hip (see fwd_chain).
-    Every h_l and probs keeps its bits.  Default on; SS_FWD_CHAIN=0
-    (read once) turns it off."""
+    Every h_l and probs keeps its bits.  A pipeline stage with no head
+    runs its layers as that kernel's stage arm (see fwd_chain_stage).
+    Default on; SS_FWD_CHAIN=0 (read once) turns both off."""
     global _FWD_CHAIN
     _FWD_CHAIN = bool(flag)
 
@@ -711,6 +714,60 @@ def fwd_chain(x, ws, bs, w_head, b_head, rows=0, waves=0, l1=0, kloop=0,
     if not out:
         return None
     return out[:-1], out[-1]
+
+
+def fwd_chain_stage(x, ws, bs, rows=0, waves=0, l1=0, kloop=0):
+    """The ReLU layers of a pipeline stage that has no head in one
+    kernel (GPU only, the stage arm of csrc/fwd_chain.hip).
+
+    ws / bs / x and rows / waves / l1 / kloop as fwd_chain.
+
+      h_l = relu(h_{l-1} @ W_l^T + b_l)
+
+    Returns [h_l, ...] (the last one is what the stage sends on), each
+    bit-identical to linear_fwd(relu) -> ..., or None, with nothing
+    launched, when the inputs are outside the kernel's contract (the
+    caller takes the per-layer path)."""
+    if not _is_gpu(x):
+        return None
+    out = _ext_for(x).fwd_chain_stage(x, list(ws), list(bs), int(rows),
+                                      int(waves), int(l1), int(kloop))
+    return out or None
+
+
+def bwd_chain_stage(dout, hs, w_ts, rows=0, waves=0, w_lds=0, dz_scale=1.0):
+    """The ReLU-layer data gradients of a pipeline stage that has no
+    head in one kernel (GPU only, the stage arm of csrc/bwd_chain.hip).
+
+    dout: the gradient of the top layer's output, (M, 256), as received
+    from the next stage.  hs / w_ts as bwd_chain: post-ReLU outputs, top
+    layer first, and the transposed weights of the layers whose dgrad is
+    in the chain — all of them (dx of the last layer is returned) or all
+    but the last (the chain ends at dz of the last layer).
+
+      dz_0 = dout ⊙ 1[h_0 > 0] ;  dh = dz_0 @ W_0 ;
+      dz_l = dh ⊙ 1[h_l > 0] ;  dh = dz_l @ W_l ;  ...
+
+    Returns ([dz_l, ...], dx or None), each bit-identical to relu_bwd ->
+    linear_dgrad -> ..., or None, with nothing launched, when the inputs
+    are outside the kernel's contract (the caller takes the per-layer
+    path).  rows / waves / w_lds select the measured arms; 0 is the
+    shipped choice: eight waves, on 32 rows where 64-row tiles would
+    cover at most half of the CUs (M <= 8192), else on 64.
+
+    dz_scale != 1 (layers under inverted dropout, all with one p): every
+    kept dz_l element is bf16(dh · dz_scale), bit-identical to
+    relu_bwd(dh, h_l, scale=dz_scale).  One scale per launch; built for
+    the eight-wave arms without w_lds, so another arm returns None."""
+    if not _is_gpu(dout):
+        return None
+    out = _ext_for(dout).bwd_chain_stage(dout, list(hs), list(w_ts),
+                                         int(rows), int(waves), int(w_lds),
+                                         float(dz_scale))
+    if not out:
+        return None
+    n = len(hs)
+    return out[:n], (out[n] if len(w_ts) == n else None)
 
 
 def xent_loss(probs, target, global_batch, eps=1e-9):
