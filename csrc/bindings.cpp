@@ -287,6 +287,54 @@ void wgrad_tn(torch::Tensor dy, torch::Tensor x, torch::Tensor gw,
                 N, Kb, (int)split_k, (int)stages, cur_stream());
 }
 
+// Ordered split-K wgrad (bitwise reproducible at full width): partial
+// tiles to a workspace, then the fold.  The workspace is a torch::empty
+// on the current device and stream, so the call is legal under graph
+// capture like the other bindings' outputs.
+void wgrad_tn_ordered(torch::Tensor dy, torch::Tensor x, torch::Tensor gw,
+                      torch::Tensor gb, torch::Tensor mask,
+                      int64_t split_k) {
+    check_bf16(dy, "dy");
+    check_bf16(x, "x");
+    check_f32(gw, "gw");
+    const int Kb = dy.size(0), Mo = dy.size(1), N = x.size(1);
+    TORCH_CHECK(x.size(0) == Kb, "batch mismatch");
+    TORCH_CHECK(gw.size(0) == Mo && gw.size(1) == N, "gw shape");
+    const void* mask_p = opt_bf16(mask, "mask");
+    TORCH_CHECK(!mask_p || mask.sizes() == dy.sizes(), "mask must match dy");
+    void* gb_p = opt_f32(gb, "gb");
+    TORCH_CHECK(!gb_p || gb.numel() == Mo, "gb size");
+    TORCH_CHECK(Kb >= 1 && Mo >= 1 && N >= 1, "empty problem");
+    TORCH_CHECK(split_k >= 0 && split_k <= INT_MAX, "split_k must be >= 0");
+    const size_t bytes =
+        ss_wgrad_ordered_plan(Mo, N, Kb, (int)split_k, nullptr, nullptr);
+    torch::Tensor part;
+    if (bytes)
+        part = torch::empty({(int64_t)bytes},
+                            dy.options().dtype(torch::kUInt8));
+    TORCH_CHECK(ss_wgrad_tn_ordered(dy.data_ptr(), x.data_ptr(), mask_p,
+                                    gw.data_ptr(), gb_p,
+                                    bytes ? part.data_ptr() : nullptr, bytes,
+                                    Mo, N, Kb, (int)split_k, cur_stream()),
+                "wgrad_tn_ordered: bad shape, split or pointer");
+}
+
+// (effective split, blocks of the partial launch, workspace bytes) of
+// wgrad_tn_ordered for a shape.  Host only.
+std::tuple<int64_t, int64_t, int64_t> wgrad_ordered_plan(int64_t Kb,
+                                                         int64_t Mo,
+                                                         int64_t N,
+                                                         int64_t split_k) {
+    TORCH_CHECK(Kb >= 1 && Mo >= 1 && N >= 1 && Kb <= INT_MAX &&
+                    Mo <= INT_MAX && N <= INT_MAX,
+                "shape (Kb, Mo, N)");
+    TORCH_CHECK(split_k >= 0 && split_k <= INT_MAX, "split_k must be >= 0");
+    int split = 0, blocks = 0;
+    const size_t bytes = ss_wgrad_ordered_plan((int)Mo, (int)N, (int)Kb,
+                                               (int)split_k, &split, &blocks);
+    return {split, blocks, (int64_t)bytes};
+}
+
 void wgrad_tn_multi(torch::Tensor chunk_table, int64_t nchunks,
                     bool has_mask, torch::Tensor gw, torch::Tensor gb,
                     int64_t Mo, int64_t N, int64_t kb_chunk,
@@ -960,6 +1008,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "staging sets of the K loop (0 = the launcher's choice)",
           py::arg("dy"), py::arg("x"), py::arg("gw"), py::arg("gb"),
           py::arg("mask"), py::arg("split_k"), py::arg("stages") = 0);
+    m.def("wgrad_tn_ordered", &wgrad_tn_ordered,
+          "gw += (dy*mask)^T @ x, gb += colsum: split-K partials to a "
+          "workspace, folded in slice order (bitwise reproducible)",
+          py::arg("dy"), py::arg("x"), py::arg("gw"), py::arg("gb"),
+          py::arg("mask"), py::arg("split_k") = 0);
+    m.def("wgrad_ordered_plan", &wgrad_ordered_plan,
+          "(split, blocks, workspace bytes) of wgrad_tn_ordered; host only",
+          py::arg("Kb"), py::arg("Mo"), py::arg("N"), py::arg("split_k") = 0);
     m.def("wgrad_tn_group", &wgrad_tn_group,
           "unmasked wgrads of a list of (dy, x, gw, gb): consecutive "
           "problems of one tile configuration share a launch",

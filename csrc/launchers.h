@@ -13,6 +13,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <cstddef>
 #include <cstdint>
 
 // Non-null and 16-byte aligned: what a kernel that moves 16-byte pieces
@@ -71,6 +72,28 @@ void ss_wgrad_tn_multi(const void* chunk_table, int nchunks, bool has_mask,
                        int split_k, hipStream_t stream);
 bool ss_wgrad_tn_256(const void* dY, const void* X, void* gW, int Mo, int N,
                      int Kb, hipStream_t stream);
+
+// Ordered split-K: the bitwise-reproducible wgrad at full width.  Each
+// K-slice's partial tile goes to the workspace `part` by plain stores
+// and a fold kernel leaves
+//     gW = gW_old + (((p_0 + p_1) + p_2) + ... + p_{S-1})
+// in f32, gb likewise: a pure function of the shapes and the build.
+// split_k: 0 = one wave of blocks, as the default path's auto split;
+// else the caller's, lowered to whole 64-row K-steps.  An effective
+// split of 1 IS ss_wgrad_tn(..., split_k = 1): no workspace, no fold.
+// The 256-tile tier (atomics) is never entered.  `part`: device memory,
+// 16-byte aligned, part_bytes >= ss_wgrad_ordered_plan's; its contents
+// before and after the call mean nothing.  False, with nothing launched,
+// for a bad shape, split, pointer or a workspace too small.
+bool ss_wgrad_tn_ordered(const void* dY, const void* X, const void* mask,
+                         void* gW, void* gb, void* part, size_t part_bytes,
+                         int Mo, int N, int Kb, int split_k,
+                         hipStream_t stream);
+// Host only: the workspace bytes of that call (0 when the split is 1),
+// its effective split and the blocks of its partial launch.  With
+// split_k = 0 at most 256 blocks of one tile (<= 64 KB) each: <= 16 MB.
+size_t ss_wgrad_ordered_plan(int Mo, int N, int Kb, int split_k, int* split,
+                             int* blocks);
 
 // Grouped launch: independent unmasked problems, side by side.
 constexpr int SS_WGRAD_GROUP_MAX = 8;  // problems per launch

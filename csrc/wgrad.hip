@@ -171,6 +171,148 @@ void wgrad_group_kernel(const WgradGroupArgs args) {
 #undef WGRAD_DECODE
 #undef WGRAD_DB_OWNER
 
+// ------------------------------------------- ordered split-K (bitwise)
+//
+// Determinism needs a fixed summation ORDER, not a single owner.  The
+// tile body already sums its K-groups through LDS in group order; only
+// the f32 atomics across blocks depend on arrival.  wgrad_part_kernel is
+// that body with another way out: block (m-tile, n-tile, slice s) STORES
+// its summed band to part[s][Mo][N] and the bias owner its row sums to
+// partb[s][Mo]: plain row-contiguous stores, 16 B per lane when N % 4
+// == 0 (the slice base s * Mo * N is then 16-B aligned as well).  No
+// atomics, no inter-block protocol, no ticket.  Every block writes all
+// of its tile that lies inside the matrix, also when its K-range gives
+// it nothing to add, so the workspace needs no clearing.
+// wgrad_fold_kernel then leaves
+//     gW = gW_old + (((p_0 + p_1) + p_2) + ... + p_{S-1})
+// (gb from partb likewise), in f32, slice order: grad += semantics, and
+// successive calls on one stream (µbatches) stay ordered.
+#define WGRAD_DECODE                                                        \
+    const int gx = gridDim.x, gy = gridDim.y;                               \
+    const int nwg = gx * gy * gridDim.z;                                    \
+    const int hw = blockIdx.x + gx * (blockIdx.y + gy * blockIdx.z);        \
+    const int wid = xcd_remap(hw, nwg);                                     \
+    const int bidy = wid % gy;                                              \
+    const int bidx = (wid / gy) % gx;                                       \
+    const int bidz = wid / (gy * gx);                                       \
+    const gbf16* const gdY = (const gbf16*)dY;                              \
+    const gbf16* const gX = (const gbf16*)X;                                \
+    const gbf16* const gmask = (const gbf16*)mask;                          \
+    const int m0 = bidx * BMT;                                              \
+    const int n0 = bidy * BNT;                                              \
+    const int kbeg = bidz * k_per_split;                                    \
+    const int kend = min(Kb, kbeg + k_per_split);
+#define WGRAD_DB_OWNER bidy == 0
+#define WGRAD_EPI_DB(row, s) partb[(long)bidz * Mo + (row)] = (s)
+// a lane takes four consecutive floats of a band row (BNT % 4 == 0):
+// with N % 4 == 0 they are inside the matrix together
+#define WGRAD_EPI_BAND                                                      \
+    {                                                                       \
+        float* const slice = part + (long)bidz * Mo * N;                    \
+        const bool vec4 = (N & 3) == 0;                                     \
+        for (int ix = tid * 4; ix < RP * BNT; ix += NT * 4) {               \
+            const int grow = m0 + p * RP + ix / BNT;                        \
+            const int gcol = n0 + ix % BNT;                                 \
+            if (grow >= Mo || gcol >= N) continue;                          \
+            float* const dst = slice + (long)grow * N + gcol;               \
+            const f32x4 v = *(const f32x4*)&red[ix];                        \
+            if (vec4) {                                                     \
+                *(f32x4*)dst = v;                                           \
+            } else {                                                        \
+                _Pragma("unroll") for (int e = 0; e < 4; ++e)               \
+                    if (gcol + e < N) dst[e] = v[e];                        \
+            }                                                               \
+        }                                                                   \
+    }
+
+template <int BMT, int BNT, bool HAS_MASK, int KG, int NSTAGE>
+__global__ __launch_bounds__(KG * 256, BMT* BNT > 64 * 64 ? 2 : 4)
+void wgrad_part_kernel(
+    const __bf16* __restrict__ dY,    // [Kb][Mo]
+    const __bf16* __restrict__ X,     // [Kb][N]
+    const __bf16* __restrict__ mask,  // [Kb][Mo]
+    float* __restrict__ part,         // [split][Mo][N], 16-B aligned
+    float* __restrict__ partb,        // [split][Mo] or null
+    int Mo, int N, int Kb, int k_per_split) {
+    __shared__ __attribute__((aligned(16)))
+    ushort smem[NSTAGE * wgrad_set_el<BMT, BNT, KG>()];
+    float* const gb = partb;  // the body asks it whether there is a bias
+#define WGRAD_TILE_HERE
+#include "wgrad_dev.h"
+}
+#undef WGRAD_DECODE
+#undef WGRAD_DB_OWNER
+#undef WGRAD_EPI_DB
+#undef WGRAD_EPI_BAND
+
+// a + b as ONE v_add_f32: behind an empty asm a lane's four sums are not
+// paired into packed f32 adds
+__device__ __forceinline__ float fold_add(float a, float b) {
+    float r = a + b;
+    asm("" : "+v"(r));
+    return r;
+}
+
+// One thread owns four consecutive floats of gW (threads [0, nw4)), the
+// threads after them four consecutive rows of gb.  vec: gW is 16-B
+// aligned and Mo * N % 4 == 0, so every slice is too.  The sums are
+// written one float at a time: the order is the contract.
+__global__ __launch_bounds__(256)
+void wgrad_fold_kernel(const float* __restrict__ part,   // [S][MN]
+                       const float* __restrict__ partb,  // [S][Mo]
+                       float* __restrict__ gW, float* __restrict__ gb,
+                       long MN, int Mo, int S, int vec) {
+    const long nw4 = (MN + 3) / 4;
+    const long t = (long)blockIdx.x * 256 + threadIdx.x;
+    if (t < nw4) {
+        const long o = t * 4;
+        if (vec) {
+            // gW first: its load runs under the slices'
+            f32x4 g = *(const f32x4*)(gW + o);
+            f32x4 a;
+            int s = 0;
+            // B slices' loads in flight, then their sums in order:
+            // runs of 16, then of 4, then single slices
+            auto run = [&](auto bc) {
+                constexpr int B = decltype(bc)::value;
+                for (; s + B <= S; s += B) {
+                    f32x4 b[B];
+#pragma unroll
+                    for (int j = 0; j < B; ++j)
+                        b[j] = *(const f32x4*)(part + (s + j) * MN + o);
+                    if (s == 0) a = b[0];  // t = p0
+#pragma unroll
+                    for (int j = 0; j < B; ++j)
+#pragma unroll
+                        for (int e = 0; e < 4; ++e)
+                            a[e] = j == 0 && s == 0 ? a[e]
+                                                    : fold_add(a[e], b[j][e]);
+                }
+            };
+            run(std::integral_constant<int, 16>{});
+            run(std::integral_constant<int, 4>{});
+            run(std::integral_constant<int, 1>{});
+#pragma unroll
+            for (int e = 0; e < 4; ++e) g[e] = fold_add(g[e], a[e]);
+            *(f32x4*)(gW + o) = g;
+        } else {
+            for (long i = o; i < o + 4 && i < MN; ++i) {
+                float a = part[i];
+                for (int s = 1; s < S; ++s) a = fold_add(a, part[s * MN + i]);
+                gW[i] = fold_add(gW[i], a);
+            }
+        }
+        return;
+    }
+    if (!gb) return;
+    const long o = (t - nw4) * 4;
+    for (long i = o; i < o + 4 && i < Mo; ++i) {
+        float a = partb[i];
+        for (int s = 1; s < S; ++s) a = fold_add(a, partb[(long)s * Mo + i]);
+        gb[i] = fold_add(gb[i], a);
+    }
+}
+
 // ------------------------------------------------------------ dispatch
 
 namespace {
@@ -505,5 +647,101 @@ bool ss_wgrad_tn_group(const WgradProblem* p, int n, const int* splits,
             hipLaunchKernelGGL((wgrad_group_kernel<64, 64, 4, 2>), grid,
                                dim3(4 * 256), 0, stream, args);
     }
+    return true;
+}
+
+// ---------------------------------------------------- ordered split-K
+
+namespace {
+
+// Tile and split of the ordered path.  The tile is wgrad_cfg's and the
+// K-groups the shipped ones of its regime (KG = 1 with 2x - 8x the
+// slices measured slower at every flagship shape: docs/KERNELS.md);
+// split_k = 0 aims at one wave of blocks as wgrad_auto_split does, an
+// explicit split goes through wgrad_eff_split.
+struct WgradOrderedPlan {
+    WgradCfg cfg;
+    int split, tiles;
+    size_t partb_off, bytes;  // partb within the workspace; its size
+};
+
+WgradOrderedPlan wgrad_ordered_plan(int Mo, int N, int Kb, int split_k) {
+    WgradOrderedPlan pl;
+    pl.cfg = wgrad_cfg(Mo, N, 0);
+    pl.cfg.kg = pl.cfg.bn == 64 ? WGRAD_KG_64 : WGRAD_KG_128;
+    pl.tiles = cdiv(Mo, pl.cfg.bm) * cdiv(N, pl.cfg.bn);
+    if (split_k <= 0) split_k = wgrad_auto_split(pl.tiles, Kb, pl.cfg.kg);
+    pl.split = wgrad_eff_split(Kb, split_k);
+    // part[split][Mo][N], then partb[split][Mo] from the next 16 B.
+    // Auto split: split * tiles <= 256 blocks of at most 128 x 128 x 4
+    // B, so at most 16 MB; an explicit split is the caller's to size.
+    pl.partb_off = ((size_t)pl.split * Mo * N * 4 + 15) & ~(size_t)15;
+    pl.bytes = pl.split > 1 ? pl.partb_off + (size_t)pl.split * Mo * 4 : 0;
+    return pl;
+}
+
+template <int BMT, int BNT, int KGV, class... Args>
+void wgrad_part_launch(bool has_mask, int stages, dim3 grid,
+                       hipStream_t stream, Args... args) {
+    if (has_mask)
+        hipLaunchKernelGGL((wgrad_part_kernel<BMT, BNT, true, KGV, 1>), grid,
+                           dim3(KGV * 256), 0, stream, args...);
+    else if (stages == 2)
+        hipLaunchKernelGGL((wgrad_part_kernel<BMT, BNT, false, KGV, 2>), grid,
+                           dim3(KGV * 256), 0, stream, args...);
+    else
+        hipLaunchKernelGGL((wgrad_part_kernel<BMT, BNT, false, KGV, 1>), grid,
+                           dim3(KGV * 256), 0, stream, args...);
+}
+
+}  // namespace
+
+size_t ss_wgrad_ordered_plan(int Mo, int N, int Kb, int split_k, int* split,
+                             int* blocks) {
+    const WgradOrderedPlan pl = wgrad_ordered_plan(Mo, N, Kb, split_k);
+    if (split) *split = pl.split;
+    if (blocks) *blocks = pl.split * pl.tiles;
+    return pl.bytes;
+}
+
+bool ss_wgrad_tn_ordered(const void* dY, const void* X, const void* mask,
+                         void* gW, void* gb, void* part, size_t part_bytes,
+                         int Mo, int N, int Kb, int split_k,
+                         hipStream_t stream) {
+    if (Mo < 1 || N < 1 || Kb < 1 || split_k < 0) return false;
+    const WgradOrderedPlan pl = wgrad_ordered_plan(Mo, N, Kb, split_k);
+    if (pl.split == 1) {
+        // one slice: today's single-owner launch, no workspace, no fold
+        ss_wgrad_tn(dY, X, mask, gW, gb, Mo, N, Kb, 1, 0, stream);
+        return true;
+    }
+    if (!aligned16(part) || part_bytes < pl.bytes || !gW ||
+        ((uintptr_t)gW & 3) || ((uintptr_t)gb & 3))
+        return false;
+    const WgradCfg& cfg = pl.cfg;
+    const int k_per_split = cdiv(cdiv(Kb, pl.split), 64) * 64;
+    const dim3 grid(cdiv(Mo, cfg.bm), cdiv(N, cfg.bn), pl.split);
+    const bool has_mask = mask != nullptr;
+    // two staging sets where wgrad_tn_kernel measured them faster:
+    // unmasked launches whose grid has full tiles
+    const int stages = !has_mask && Mo >= cfg.bm && N >= cfg.bn ? 2 : 1;
+    float* const partw = (float*)part;
+    float* const partb = gb ? (float*)((char*)part + pl.partb_off) : nullptr;
+#define WGRAD_PART(BMT, BNT, KGV)                                           \
+    wgrad_part_launch<BMT, BNT, KGV>(                                       \
+        has_mask, stages, grid, stream, (const __bf16*)dY,                  \
+        (const __bf16*)X, (const __bf16*)mask, partw, partb, Mo, N, Kb,     \
+        k_per_split)
+    if (cfg.bm == 128) WGRAD_PART(128, 128, WGRAD_KG_128);
+    else if (cfg.bn == 128) WGRAD_PART(64, 128, WGRAD_KG_128);
+    else WGRAD_PART(64, 64, WGRAD_KG_64);
+#undef WGRAD_PART
+    const long MN = (long)Mo * N;
+    const long threads = (MN + 3) / 4 + (gb ? cdiv(Mo, 4) : 0);
+    const int vec = aligned16(gW) && (MN & 3) == 0;
+    const dim3 fold_grid((unsigned)((threads + 255) / 256));
+    hipLaunchKernelGGL(wgrad_fold_kernel, fold_grid, dim3(256), 0, stream,
+                       (const float*)partw, (const float*)partb, (float*)gW,
+                       (float*)gb, MN, Mo, pl.split, vec);
     return true;
 }

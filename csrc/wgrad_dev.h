@@ -27,6 +27,13 @@
 //     int m0, n0;                       tile origin
 //     bool db_owner;                    this block adds gb (n-tile 0)
 //     int kbeg, kend;                   K-range
+//
+// Two optional hooks replace the ways out of the epilogue; undefined,
+// the text is the f32 atomics into gb / gW:
+//     WGRAD_EPI_DB(row, s)   what the bias owner does with row's sum s
+//     WGRAD_EPI_BAND         statements that write out band p of the
+//                            summed tile: red[RP][BNT], tile rows from
+//                            p * RP (wgrad_part_kernel's plain stores)
 #ifndef SS_WGRAD_DEV_H
 #define SS_WGRAD_DEV_H
 
@@ -473,7 +480,11 @@ __device__ __forceinline__ void wgrad_two_sets(ushort* __restrict__ cur,
             float s = 0.f;
 #pragma unroll
             for (int qq = 0; qq < NQ; ++qq) s += red[qq * BMT + tid];
+#ifdef WGRAD_EPI_DB
+            WGRAD_EPI_DB(m0 + tid, s);
+#else
             atomicAdd(&gb[m0 + tid], s);
+#endif
         }
         __syncthreads();
     }
@@ -510,6 +521,10 @@ __device__ __forceinline__ void wgrad_two_sets(ushort* __restrict__ cur,
             }
             __syncthreads();
         }
+#ifdef WGRAD_EPI_BAND
+        // the including kernel's own way out for the band (pass p)
+        WGRAD_EPI_BAND
+#else
         // ONE set of atomics per block, row-contiguous: a wave
         // instruction covers 64 consecutive floats of one gW row
         for (int ix = tid; ix < RP * BNT; ix += NT) {
@@ -518,6 +533,7 @@ __device__ __forceinline__ void wgrad_two_sets(ushort* __restrict__ cur,
             if (grow < Mo && gcol < N)
                 atomicAdd(&gW[(long)grow * N + gcol], red[ix]);
         }
+#endif
         if (p + 1 < NPASS) __syncthreads();
     }
 }

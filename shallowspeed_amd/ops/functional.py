@@ -26,26 +26,58 @@ from ._ext import load_ext
 
 
 _DETERMINISTIC = False
+_DET_WGRAD = None      # "single" | "ordered"; None = the default below
+_DET_WGRAD_ENV = None  # SS_DET_WGRAD, read once
+_DET_WGRAD_MODES = ("single", "ordered")
 
 
-def set_deterministic(flag: bool):
+def set_deterministic(flag: bool, wgrad=None):
     """Bitwise run-to-run reproducible GPU training.
 
-    Forces the single-owner (split_k=1) wgrad path so f32 atomicAdd
+    The weight gradients then sum in a fixed order, so f32 atomicAdd
     ARRIVAL ORDER cannot perturb gradient bits; all other hot kernels
     (fwd/dgrad GEMMs, fused SGD, loss heads) are deterministic by
     construction (fixed tile ownership, no atomics), and the DP bucket
     all-reduce order is fixed by construction in GradReducer.  Matches
     the reference's exact-equality replica gate (train.py:154-155) at
-    the bitwise level on GPU.  Costs wgrad parallelism on small-M
-    shapes (split-K is what fills the chip there) — opt-in via
-    --deterministic."""
-    global _DETERMINISTIC
+    the bitwise level on GPU.  Opt-in via --deterministic.
+
+    wgrad picks how the order is fixed:
+      "single"   the single-owner (split_k=1) path: one block walks the
+                 whole batch of its output tile.  Costs wgrad parallelism
+                 on small-M shapes (split-K is what fills the chip
+                 there).
+      "ordered"  split-K at full width: each slice's partial tile goes to
+                 a workspace by plain stores and a second kernel adds the
+                 partials in slice order (ext.wgrad_tn_ordered).
+      None       SS_DET_WGRAD (read once), else "single".
+    The two modes differ in f32 summation order, so in bits; each is a
+    pure function of shapes and build."""
+    global _DETERMINISTIC, _DET_WGRAD
+    if wgrad is not None and wgrad not in _DET_WGRAD_MODES:
+        raise ValueError(f"wgrad must be one of {_DET_WGRAD_MODES}")
+    _DET_WGRAD = wgrad
     _DETERMINISTIC = bool(flag)
 
 
 def deterministic() -> bool:
     return _DETERMINISTIC
+
+
+def deterministic_wgrad() -> str:
+    """The deterministic mode's wgrad path, "single" or "ordered": what
+    the last set_deterministic named, else SS_DET_WGRAD, else "single"."""
+    global _DET_WGRAD_ENV
+    if _DET_WGRAD is not None:
+        return _DET_WGRAD
+    if _DET_WGRAD_ENV is None:
+        import os
+
+        mode = os.environ.get("SS_DET_WGRAD", "single")
+        if mode not in _DET_WGRAD_MODES:
+            raise ValueError(f"SS_DET_WGRAD must be one of {_DET_WGRAD_MODES}")
+        _DET_WGRAD_ENV = mode
+    return _DET_WGRAD_ENV
 
 
 _HEAD_FUSED = None
@@ -294,7 +326,8 @@ def _dgrad_lib_enabled() -> bool:
     return _DGRAD_LIB
 
 
-def linear_wgrad_acc(dy, x, grad_w, grad_b=None, mask_src=None, split_k=0):
+def linear_wgrad_acc(dy, x, grad_w, grad_b=None, mask_src=None, split_k=0,
+                     ordered=False):
     """grad_w += (dy ⊙ mask)^T @ x ; grad_b += colsum(dy ⊙ mask).
 
     Accumulates IN PLACE into f32 grad buffers — this is how both
@@ -302,21 +335,26 @@ def linear_wgrad_acc(dy, x, grad_w, grad_b=None, mask_src=None, split_k=0):
     split-K parallelism work: the GPU kernel uses f32 atomicAdd, so a
     K-split over the batch dimension and accumulation across µbatches
     compose for free.  split_k=0 lets the kernel pick; split_k=1 is the
-    deterministic single-owner path (forced by set_deterministic).
+    deterministic single-owner path (forced by set_deterministic in its
+    "single" mode).  ordered=True takes the ordered split-K path
+    (partials to a workspace, folded in slice order: bitwise
+    reproducible at any split); set_deterministic's "ordered" mode
+    selects it for split_k=0.
     Reference: functional.py:21 (dW = dout.T @ x, db = dout.sum(0)).
     """
     if split_k == 0 and _DETERMINISTIC:
-        split_k = 1
+        if deterministic_wgrad() == "ordered":
+            ordered = True
+        else:
+            split_k = 1
     if _is_gpu(dy):
         ext = _ext_for(dy)
-        ext.wgrad_tn(
-            dy,
-            x,
-            grad_w,
-            grad_b if grad_b is not None else torch.Tensor(),
-            mask_src if mask_src is not None else torch.Tensor(),
-            int(split_k),
-        )
+        gb = grad_b if grad_b is not None else torch.Tensor()
+        mask = mask_src if mask_src is not None else torch.Tensor()
+        if ordered:
+            ext.wgrad_tn_ordered(dy, x, grad_w, gb, mask, int(split_k))
+        else:
+            ext.wgrad_tn(dy, x, grad_w, gb, mask, int(split_k))
         return
     if mask_src is not None:
         dy = dy * (mask_src > 0).to(dy.dtype)
@@ -946,7 +984,8 @@ def linear_wgrad_multi(chunks, grad_w, grad_b=None, split_k=0):
     schedules (each launch re-pays prologue + atomic epilogue).
     GPU only; the CPU path loops (it has no launch cost to amortize).
     """
-    if split_k == 0 and _DETERMINISTIC:
+    forced = split_k == 0 and _DETERMINISTIC
+    if forced:
         split_k = 1
     dy0 = chunks[0][0]
     if not _is_gpu(dy0) or split_k == 1:
@@ -957,6 +996,11 @@ def linear_wgrad_multi(chunks, grad_w, grad_b=None, split_k=0):
         # determinism test).  Sequential per-chunk launches fix the
         # accumulation order at a small launch-count cost; perf mode
         # (split_k=0) keeps the single fused launch.
+        # In the "ordered" deterministic mode each chunk is an ordered
+        # split-K call (the caller's split_k = 0), chunks in call order.
+        if _DETERMINISTIC and deterministic_wgrad() == "ordered" \
+                and forced:
+            split_k = 0
         for dy, x, m in chunks:
             linear_wgrad_acc(dy, x, grad_w, grad_b, m, split_k)
         return

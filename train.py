@@ -104,8 +104,16 @@ def main():
                     help="linear LR warmup epochs before the schedule")
     ap.add_argument("--deterministic", action="store_true",
                     help="bitwise run-to-run reproducible GPU training "
-                         "(forces the single-owner split_k=1 wgrad path; "
+                         "(forces the single-owner split_k=1 wgrad path, or "
+                         "the one --deterministic-wgrad names; "
                          "bucket reduction order is fixed by construction)")
+    ap.add_argument("--deterministic-wgrad", choices=["single", "ordered"],
+                    default=None,
+                    help="with --deterministic: single = one block per "
+                         "output tile walks the whole batch; ordered = "
+                         "split-K partials to a workspace, folded in slice "
+                         "order (full width).  Default: SS_DET_WGRAD, else "
+                         "single")
     ap.add_argument("--fp8-fwd", action="store_true",
                     help="MX-fp8 training forward on qualifying Linears "
                          "(O%%256,I%%256,µbatch%%256); backward stays bf16, "
@@ -149,6 +157,8 @@ def main():
         ap.error("--dropout must be in [0, 1)")
     if args.dropout > 0 and args.tp > 1:
         ap.error("--dropout is not supported with --tp > 1")
+    if args.deterministic_wgrad and not args.deterministic:
+        ap.error("--deterministic-wgrad needs --deterministic")
     if not 0 <= args.dropout_seed < 1 << 64:
         ap.error("--dropout-seed must fit 64 bits")
 
@@ -165,7 +175,7 @@ def main():
     if args.deterministic:
         from shallowspeed_amd.ops import functional as _F
 
-        _F.set_deterministic(True)
+        _F.set_deterministic(True, wgrad=args.deterministic_wgrad)
 
     if args.tp > 1:
         from shallowspeed_amd.parallel import TPMLP
