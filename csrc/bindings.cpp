@@ -373,9 +373,8 @@ std::vector<int> wgrad_group_splits(
     return s;
 }
 
-void wgrad_tn_group(std::vector<WgradGroupProblem> problems,
-                    std::optional<std::vector<int64_t>> splits) {
-    // every check before the first launch: a refused call touches nothing
+std::vector<WgradProblem> wgrad_group_problems(
+    const std::vector<WgradGroupProblem>& problems) {
     std::vector<WgradProblem> p;
     for (const auto& [dy, x, gw, gb] : problems) {
         check_bf16(dy, "dy");
@@ -391,6 +390,13 @@ void wgrad_tn_group(std::vector<WgradGroupProblem> problems,
         p.push_back({dy.data_ptr(), x.data_ptr(), gw.data_ptr(), gb_p, Mo, N,
                      Kb});
     }
+    return p;
+}
+
+void wgrad_tn_group(std::vector<WgradGroupProblem> problems,
+                    std::optional<std::vector<int64_t>> splits) {
+    // every check before the first launch: a refused call touches nothing
+    const std::vector<WgradProblem> p = wgrad_group_problems(problems);
     const std::vector<int> s = wgrad_group_splits(splits, p.size());
     if (p.empty()) return;
     TORCH_CHECK(ss_wgrad_tn_group(p.data(), (int)p.size(), s.data(),
@@ -398,12 +404,42 @@ void wgrad_tn_group(std::vector<WgradGroupProblem> problems,
                 "wgrad_tn_group: bad shape, split or pointer");
 }
 
+// The ordered form (bitwise reproducible): per planned launch one
+// partial launch into the workspace and one tree fold.  The workspace
+// is a torch::empty on the current device and stream, as in
+// wgrad_tn_ordered.  fold_waves: 0 = the build's, else the arm to time.
+void wgrad_tn_group_ordered(std::vector<WgradGroupProblem> problems,
+                            std::optional<std::vector<int64_t>> splits,
+                            int64_t fold_waves) {
+    const std::vector<WgradProblem> p = wgrad_group_problems(problems);
+    const std::vector<int> s = wgrad_group_splits(splits, p.size());
+    if (p.empty()) return;
+    std::vector<WgradGroupLaunch> plan(p.size());
+    size_t bytes = 0;
+    TORCH_CHECK(ss_wgrad_group_ordered_plan(p.data(), (int)p.size(), s.data(),
+                                            plan.data(), &bytes) >= 0,
+                "wgrad_tn_group_ordered: bad shape or split");
+    torch::Tensor ws;
+    if (bytes)
+        ws = torch::empty(
+            {(int64_t)bytes},
+            std::get<0>(problems[0]).options().dtype(torch::kUInt8));
+    TORCH_CHECK(ss_wgrad_tn_group_ordered(
+                    p.data(), (int)p.size(), s.data(),
+                    bytes ? ws.data_ptr() : nullptr, bytes, cur_stream(),
+                    (int)fold_waves),
+                "wgrad_tn_group_ordered: bad shape, split or pointer");
+}
+
 // The launches wgrad_tn_group makes for these (Kb, Mo, N) shapes: per
 // launch (problem indices, splits, block counts).  Host only.
+// `ordered` non-null: those of wgrad_tn_group_ordered, and its
+// workspace bytes go to *ordered.
 std::vector<std::tuple<std::vector<int64_t>, std::vector<int64_t>,
                        std::vector<int64_t>>>
-wgrad_group_plan(std::vector<std::tuple<int64_t, int64_t, int64_t>> shapes,
-                 std::optional<std::vector<int64_t>> splits) {
+wgrad_group_plan_of(
+    const std::vector<std::tuple<int64_t, int64_t, int64_t>>& shapes,
+    const std::optional<std::vector<int64_t>>& splits, size_t* ordered) {
     std::vector<WgradProblem> p;
     for (const auto& [Kb, Mo, N] : shapes) {
         TORCH_CHECK(Kb >= 1 && Mo >= 1 && N >= 1 && Kb <= INT_MAX &&
@@ -415,7 +451,10 @@ wgrad_group_plan(std::vector<std::tuple<int64_t, int64_t, int64_t>> shapes,
     const std::vector<int> s = wgrad_group_splits(splits, p.size());
     std::vector<WgradGroupLaunch> plan(p.size());
     const int nl =
-        ss_wgrad_group_plan(p.data(), (int)p.size(), s.data(), plan.data());
+        ordered ? ss_wgrad_group_ordered_plan(p.data(), (int)p.size(),
+                                              s.data(), plan.data(), ordered)
+                : ss_wgrad_group_plan(p.data(), (int)p.size(), s.data(),
+                                      plan.data());
     TORCH_CHECK(nl >= 0, "wgrad_group_plan: bad shape or split");
     std::vector<std::tuple<std::vector<int64_t>, std::vector<int64_t>,
                            std::vector<int64_t>>> out;
@@ -429,6 +468,21 @@ wgrad_group_plan(std::vector<std::tuple<int64_t, int64_t, int64_t>> shapes,
         out.emplace_back(idx, sp, bl);
     }
     return out;
+}
+
+auto wgrad_group_plan(std::vector<std::tuple<int64_t, int64_t, int64_t>> shapes,
+                      std::optional<std::vector<int64_t>> splits) {
+    return wgrad_group_plan_of(shapes, splits, nullptr);
+}
+
+// (launches as above, workspace bytes) of wgrad_tn_group_ordered: blocks
+// are those of the partial launch, a split of 1 is a single-owner launch.
+auto wgrad_group_ordered_plan(
+    std::vector<std::tuple<int64_t, int64_t, int64_t>> shapes,
+    std::optional<std::vector<int64_t>> splits) {
+    size_t bytes = 0;
+    auto launches = wgrad_group_plan_of(shapes, splits, &bytes);
+    return std::make_pair(launches, (int64_t)bytes);
 }
 
 torch::Tensor colsum(torch::Tensor dy, torch::Tensor mask) {
@@ -1024,6 +1078,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "launches of wgrad_tn_group for (Kb, Mo, N) shapes: per launch "
           "(problem indices, splits, block counts)",
           py::arg("shapes"), py::arg("splits") = py::none());
+    m.def("wgrad_tn_group_ordered", &wgrad_tn_group_ordered,
+          "wgrad_tn_group, bitwise reproducible: per launch the split-K "
+          "partials of every problem to a workspace, then one tree fold",
+          py::arg("problems"), py::arg("splits") = py::none(),
+          py::arg("fold_waves") = 0);
+    m.def("wgrad_group_ordered_plan", &wgrad_group_ordered_plan,
+          "(launches as wgrad_group_plan, workspace bytes) of "
+          "wgrad_tn_group_ordered; host only",
+          py::arg("shapes"), py::arg("splits") = py::none());
+    m.attr("WGRAD_FOLD_WAVES") = SS_WGRAD_FOLD_WAVES;
     m.def("colsum", &colsum, "standalone column sum (bias grad)");
     m.def("wgrad_tn_multi", &wgrad_tn_multi,
           "chunked (deferred-µbatch) wgrad: one launch, many (dy,x) pairs");

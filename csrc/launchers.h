@@ -125,6 +125,35 @@ int ss_wgrad_group_plan(const WgradProblem* problems, int n,
 bool ss_wgrad_tn_group(const WgradProblem* problems, int n,
                        const int* splits, hipStream_t stream);
 
+// Ordered grouped launch: the bitwise-reproducible form of the above.
+// Each planned launch becomes ONE partial launch (every problem's
+// K-slices to its own region of `workspace` by plain stores) and ONE
+// fold launch over the same problems, which spreads a piece's S slices
+// over the W = SS_WGRAD_FOLD_WAVES waves of a block in a fixed tree:
+//     c = ceil(S / W),  q_w = ((p_{wc} + p_{wc+1}) + ...),
+//     gW = gW_old + (((q_0 + q_1) + q_2) + ...)     in f32, gb likewise:
+// a pure function of shapes, splits and the build.  For S <= W that is
+// ss_wgrad_tn_ordered's serial order at the same split, bit for bit.
+// A run of one goes through the same two kernels; a problem whose
+// effective split is 1 takes ss_wgrad_tn(..., split_k = 1) and no
+// workspace.  The 256-tile tier is never entered.  `workspace`: device
+// memory, 16-byte aligned, bytes >= ss_wgrad_group_ordered_plan's.
+// fold_waves: 0, or 4 / 8 / 16 to run another arm of the fold (a
+// measuring aid: other bits).  False, with nothing launched, for a bad
+// shape, split, pointer or a workspace too small.
+constexpr int SS_WGRAD_FOLD_WAVES = 4;  // measured: docs/KERNELS.md
+bool ss_wgrad_tn_group_ordered(const WgradProblem* problems, int n,
+                               const int* splits, void* workspace,
+                               size_t bytes, hipStream_t stream,
+                               int fold_waves = 0);
+// Host only, from the shapes alone: the launches of that call, cut where
+// ss_wgrad_group_plan cuts (blocks = those of the partial launch, a
+// split of 1 = a single-owner launch of its own), and the workspace
+// bytes.  Returns the number of launches, or -1 for a bad shape or split.
+int ss_wgrad_group_ordered_plan(const WgradProblem* problems, int n,
+                                const int* splits, WgradGroupLaunch* out,
+                                size_t* bytes);
+
 // ---- head.hip
 bool ss_head_fwd_fused(const void* x, const void* W, const void* bias,
                        void* probs, int M, int K, int C, int rows_per_block,

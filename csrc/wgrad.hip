@@ -104,8 +104,8 @@ void wgrad_tn_kernel(
 struct WgradGroupItem {
     const __bf16* dY;  // [Kb][Mo]
     const __bf16* X;   // [Kb][N]
-    float* gW;         // [Mo][N] (atomicAdd +=)
-    float* gb;         // [Mo] or null
+    float* gW;         // [Mo][N] (atomicAdd +=); ordered: part[S][Mo][N]
+    float* gb;         // [Mo] or null; ordered: partb[S][Mo] or null
     int Mo, N, Kb, k_per_split;
     int gx, gy;        // m-tiles, n-tiles
     int first;         // first work id; INT_MAX in unused slots
@@ -123,7 +123,9 @@ using gf32 = __attribute__((address_space(1))) float;
 // selects).  The pointers go through the global address space for the
 // reason given above wgrad_tn_kernel's decode; gW / gb come back as
 // plain pointers for atomicAdd and keep the inferred address space.
-#define WGRAD_DECODE                                                        \
+// (GW, GB) name the two output pointers: wgrad_group_part_kernel below
+// reads its slots' gW / gb fields as workspace bases.
+#define WGRAD_GROUP_DECODE(GW, GB)                                          \
     const int wid = xcd_remap((int)blockIdx.x, (int)gridDim.x);             \
     const gbf16* gdY = (const gbf16*)args.p[0].dY;                          \
     const gbf16* gX = (const gbf16*)args.p[0].X;                            \
@@ -146,8 +148,8 @@ using gf32 = __attribute__((address_space(1))) float;
         gy = t ? args.p[i].gy : gy;                                         \
         first = t ? args.p[i].first : first;                                \
     }                                                                       \
-    float* const gW = (float*)sgW;                                          \
-    float* const gb = (float*)sgb;                                          \
+    float* const GW = (float*)sgW;                                          \
+    float* const GB = (float*)sgb;                                          \
     const gbf16* const gmask = nullptr;                                     \
     const int lid = wid - first;                                            \
     const int bidy = lid % gy;                                              \
@@ -157,6 +159,7 @@ using gf32 = __attribute__((address_space(1))) float;
     const int n0 = bidy * BNT;                                              \
     const int kbeg = bidz * k_per_split;                                    \
     const int kend = min(Kb, kbeg + k_per_split);
+#define WGRAD_DECODE WGRAD_GROUP_DECODE(gW, gb)
 #define WGRAD_DB_OWNER bidy == 0
 
 template <int BMT, int BNT, int KG, int NSTAGE>
@@ -242,6 +245,29 @@ void wgrad_part_kernel(
 }
 #undef WGRAD_DECODE
 #undef WGRAD_DB_OWNER
+
+// wgrad_group_part_kernel: the same way out behind the grouped decode.
+// The problems of ONE grouped launch (unmasked, two staging sets) store
+// their slices side by side; a slot's gW / gb fields carry the bases of
+// its own workspace region part[S_i][Mo_i][N_i] / partb[S_i][Mo_i] (each
+// 16-B aligned; partb null = no bias).  Still no atomics, no ticket and
+// nothing to clear.
+#define WGRAD_DECODE                                                        \
+    WGRAD_GROUP_DECODE(part, partb)                                         \
+    float* const gb = partb;  // the body asks it whether there is a bias
+#define WGRAD_DB_OWNER bidy == 0
+
+template <int BMT, int BNT, int KG, int NSTAGE>
+__global__ __launch_bounds__(KG * 256, BMT* BNT > 64 * 64 ? 2 : 4)
+void wgrad_group_part_kernel(const WgradGroupArgs args) {
+    constexpr bool HAS_MASK = false;
+    __shared__ __attribute__((aligned(16)))
+    ushort smem[NSTAGE * wgrad_set_el<BMT, BNT, KG>()];
+#define WGRAD_TILE_HERE
+#include "wgrad_dev.h"
+}
+#undef WGRAD_DECODE
+#undef WGRAD_DB_OWNER
 #undef WGRAD_EPI_DB
 #undef WGRAD_EPI_BAND
 
@@ -311,6 +337,160 @@ void wgrad_fold_kernel(const float* __restrict__ part,   // [S][MN]
         for (int s = 1; s < S; ++s) a = fold_add(a, partb[(long)s * Mo + i]);
         gb[i] = fold_add(gb[i], a);
     }
+}
+
+// --------------------------------------------- grouped fold (tree, bitwise)
+//
+// wgrad_group_fold_kernel folds every problem of one grouped partial
+// launch, and spreads a piece's slices over the waves of a block where
+// wgrad_fold_kernel walks them in one lane: its time went with the
+// split, not with the bytes (profiles/r17_wgrad_ordered.md).
+//
+// A block of W waves owns one STRIP: 256 consecutive floats of one
+// problem's gW, or of its gb (further strips of the same problem).  Lane
+// l of EVERY wave owns floats [4l, 4l + 4) of the strip, so a wave
+// instruction reads 1 KB contiguous of one slice.  Wave w takes the
+// slice run [w c, min(S, (w + 1) c)), c = ceil(S / W): its loads go out
+// together (up to 8 per lane, runs of 8 beyond), then it adds them in
+// slice order and leaves its run sum q_w in LDS (W x 1 KB).  After ONE
+// barrier wave 0, whose load of gW has been in flight since kernel
+// entry, adds the non-empty q_w in wave order and stores gW + t:
+//     q_w = ((p_{wc} + p_{wc+1}) + ...),
+//     gW  = gW_old + (((q_0 + q_1) + q_2) + ...)            in f32,
+// gb likewise: a pure function of shapes, splits and W.  For S <= W
+// every run is one slice and this is wgrad_fold_kernel's serial order.
+struct WgradFoldItem {
+    const float* part;   // [S][MN], 16-B aligned
+    const float* partb;  // [S][Mo] or null
+    float* gW;           // [MN] +=
+    float* gb;           // [Mo] += or null
+    long MN;
+    int Mo, S;
+    int first;           // first block; INT_MAX in unused slots
+};
+struct WgradFoldArgs {
+    WgradFoldItem p[SS_WGRAD_GROUP_MAX];
+};
+
+using gf32x4 = __attribute__((address_space(1))) f32x4;
+
+// Four floats of a lane at p.  VEC: one 16-B access (p 16-B aligned,
+// all four inside); else the `left` (> 0) of them that lie inside, one
+// float at a time.
+template <bool VEC>
+__device__ __forceinline__ f32x4 fold_ld4(const gf32* p, long left) {
+    if constexpr (VEC) return *(const gf32x4*)p;
+    f32x4 v = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+        if (e < left) v[e] = p[e];
+    return v;
+}
+
+// One wave's part of a strip: src[S][len] + o are the lane's floats of
+// slice 0, dst + o those of the gradient.
+template <int W, bool VEC>
+__device__ __forceinline__ void fold_strip(const gf32* src, gf32* dst,
+                                           long len, long o, int S, int w,
+                                           int lane, f32x4 (*q)[64]) {
+    const bool in = o < len;
+    const long left = len - o;
+    const int c = (S + W - 1) / W;
+    const int nq = (S + c - 1) / c;  // waves with a run
+    f32x4 g;
+    if (w == 0 && in) g = fold_ld4<VEC>(dst + o, left);
+    const int s0 = w * c, s1 = min(S, s0 + c);
+    if (in && s0 < s1) {
+        f32x4 a;
+        int s = s0;
+        // B loads in flight, then their sums in slice order.  A run's
+        // last batch is the smallest of 1, 2, 4, 8 that holds it: the
+        // slots past the run load its last slice again and are dropped.
+        auto batch = [&](auto bc) {
+            constexpr int B = decltype(bc)::value;
+            f32x4 b[B];
+#pragma unroll
+            for (int j = 0; j < B; ++j)
+                b[j] = fold_ld4<VEC>(src + min(s + j, s1 - 1) * len + o,
+                                     left);
+            if (s == s0) a = b[0];
+#pragma unroll
+            for (int j = 0; j < B; ++j)
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+                    a[e] = (j == 0 && s == s0) || s + j >= s1
+                               ? a[e]
+                               : fold_add(a[e], b[j][e]);
+            s += B;
+        };
+        while (s1 - s > 8) batch(std::integral_constant<int, 8>{});
+        const int r = s1 - s;
+        if (r > 4) batch(std::integral_constant<int, 8>{});
+        else if (r > 2) batch(std::integral_constant<int, 4>{});
+        else if (r > 1) batch(std::integral_constant<int, 2>{});
+        else batch(std::integral_constant<int, 1>{});
+        q[w][lane] = a;
+    }
+    __syncthreads();
+    if (w != 0 || !in) return;
+    f32x4 t = q[0][lane];
+#pragma unroll
+    for (int k = 1; k < W; ++k) {
+        const f32x4 qk = q[k][lane];
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+            t[e] = k < nq ? fold_add(t[e], qk[e]) : t[e];
+    }
+#pragma unroll
+    for (int e = 0; e < 4; ++e) g[e] = fold_add(g[e], t[e]);
+    if constexpr (VEC) {
+        *(gf32x4*)(dst + o) = g;
+    } else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+            if (e < left) dst[o + e] = g[e];
+    }
+}
+
+template <int W>
+__global__ __launch_bounds__(W * 64)
+void wgrad_group_fold_kernel(const WgradFoldArgs args) {
+    __shared__ __attribute__((aligned(16))) f32x4 q[W][64];
+    const int lane = threadIdx.x & 63;
+    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    // the block's problem: constant-index selects, as in the grouped
+    // decode above
+    const int bid = blockIdx.x;
+    const gf32* part = (const gf32*)args.p[0].part;
+    const gf32* partb = (const gf32*)args.p[0].partb;
+    gf32* gW = (gf32*)args.p[0].gW;
+    gf32* gb = (gf32*)args.p[0].gb;
+    long MN = args.p[0].MN;
+    int Mo = args.p[0].Mo, S = args.p[0].S, first = 0;
+#pragma unroll
+    for (int i = 1; i < SS_WGRAD_GROUP_MAX; ++i) {
+        const bool t = bid >= args.p[i].first;
+        part = t ? (const gf32*)args.p[i].part : part;
+        partb = t ? (const gf32*)args.p[i].partb : partb;
+        gW = t ? (gf32*)args.p[i].gW : gW;
+        gb = t ? (gf32*)args.p[i].gb : gb;
+        MN = t ? args.p[i].MN : MN;
+        Mo = t ? args.p[i].Mo : Mo;
+        S = t ? args.p[i].S : S;
+        first = t ? args.p[i].first : first;
+    }
+    // strips of gW, then (the launcher counts them only with a bias)
+    // strips of gb
+    const long strip = bid - first, nws = (MN + 255) / 256;
+    const bool bias = strip >= nws;
+    const gf32* const src = bias ? partb : part;
+    gf32* const dst = bias ? gb : gW;
+    const long len = bias ? (long)Mo : MN;
+    const long o = (bias ? strip - nws : strip) * 256 + lane * 4;
+    const bool vec = (((uintptr_t)src | (uintptr_t)dst) & 15) == 0 &&
+                     (len & 3) == 0;
+    if (vec) fold_strip<W, true>(src, dst, len, o, S, w, lane, q);
+    else fold_strip<W, false>(src, dst, len, o, S, w, lane, q);
 }
 
 // ------------------------------------------------------------ dispatch
@@ -743,5 +923,161 @@ bool ss_wgrad_tn_ordered(const void* dY, const void* X, const void* mask,
     hipLaunchKernelGGL(wgrad_fold_kernel, fold_grid, dim3(256), 0, stream,
                        (const float*)partw, (const float*)partb, (float*)gW,
                        (float*)gb, MN, Mo, pl.split, vec);
+    return true;
+}
+
+// -------------------------------------------- ordered grouped launch
+
+namespace {
+
+// One launch of the ordered grouped plan: ss_wgrad_group_plan's cut, the
+// tile of wgrad_cfg with the shipped K-groups of its regime (the three
+// forms wgrad_group_part_kernel is built for, as wgrad_ordered_plan
+// picks them), wgrad_group_splits' splits, and each problem's workspace
+// region: part[split][Mo][N], then partb[split][Mo], both from a 16-B
+// boundary (a problem at split 1 has none).
+struct WgradGroupOrderedLaunch {
+    WgradCfg cfg;
+    WgradGroupLaunch l;
+    size_t part_off[SS_WGRAD_GROUP_MAX], partb_off[SS_WGRAD_GROUP_MAX];
+};
+
+int wgrad_group_ordered_plan(const WgradProblem* p, int n, const int* splits,
+                             WgradGroupOrderedLaunch* out, size_t* bytes) {
+    std::vector<WgradGroupLaunch> cuts(n > 0 ? n : 0);
+    const int nl = ss_wgrad_group_plan(p, n, splits, cuts.data());
+    size_t off = 0;
+    for (int l = 0; l < nl; ++l) {
+        WgradGroupOrderedLaunch& L = out[l];
+        L.l = cuts[l];
+        const WgradProblem* q = p + L.l.first;
+        L.cfg = wgrad_cfg(q->Mo, q->N, 0);
+        L.cfg.kg = L.cfg.bn == 64 ? WGRAD_KG_64 : WGRAD_KG_128;
+        int tiles[SS_WGRAD_GROUP_MAX], kb[SS_WGRAD_GROUP_MAX];
+        for (int k = 0; k < L.l.count; ++k) {
+            tiles[k] = cdiv(q[k].Mo, L.cfg.bm) * cdiv(q[k].N, L.cfg.bn);
+            kb[k] = q[k].Kb;
+            L.l.split[k] = splits ? splits[L.l.first + k] : 0;
+        }
+        wgrad_group_splits(L.l.count, tiles, kb, L.cfg.kg, L.l.split);
+        for (int k = 0; k < L.l.count; ++k) {
+            const size_t S = L.l.split[k];
+            L.l.blocks[k] = tiles[k] * L.l.split[k];
+            L.part_off[k] = L.partb_off[k] = off;
+            if (S == 1) continue;
+            L.partb_off[k] =
+                off + ((S * q[k].Mo * q[k].N * 4 + 15) & ~(size_t)15);
+            off = L.partb_off[k] + ((S * q[k].Mo * 4 + 15) & ~(size_t)15);
+        }
+    }
+    if (bytes) *bytes = off;
+    return nl;
+}
+
+template <int BMT, int BNT, int KGV>
+void wgrad_group_part_launch(int nblocks, hipStream_t stream,
+                             const WgradGroupArgs& args) {
+    hipLaunchKernelGGL((wgrad_group_part_kernel<BMT, BNT, KGV, 2>),
+                       dim3(nblocks), dim3(KGV * 256), 0, stream, args);
+}
+
+}  // namespace
+
+int ss_wgrad_group_ordered_plan(const WgradProblem* p, int n,
+                                const int* splits, WgradGroupLaunch* out,
+                                size_t* bytes) {
+    std::vector<WgradGroupOrderedLaunch> plan(n > 0 ? n : 0);
+    const int nl = wgrad_group_ordered_plan(p, n, splits, plan.data(), bytes);
+    for (int l = 0; l < nl; ++l) out[l] = plan[l].l;
+    return nl;
+}
+
+bool ss_wgrad_tn_group_ordered(const WgradProblem* p, int n,
+                               const int* splits, void* workspace,
+                               size_t bytes, hipStream_t stream,
+                               int fold_waves) {
+    if (n == 0) return true;
+    // every check first: a refused call launches nothing
+    std::vector<WgradGroupOrderedLaunch> plan(n > 0 ? n : 0);
+    size_t need = 0;
+    const int nl = wgrad_group_ordered_plan(p, n, splits, plan.data(), &need);
+    if (nl < 0) return false;
+    if (fold_waves == 0) fold_waves = SS_WGRAD_FOLD_WAVES;
+    if (fold_waves != 4 && fold_waves != 8 && fold_waves != 16) return false;
+    if (need && (!workspace || !aligned16(workspace) || bytes < need))
+        return false;
+    for (int i = 0; i < n; ++i)
+        if (!aligned16(p[i].dY) || !aligned16(p[i].X) || !p[i].gW ||
+            ((uintptr_t)p[i].gW & 3) || ((uintptr_t)p[i].gb & 3))
+            return false;
+    for (int l = 0; l < nl; ++l) {
+        const WgradGroupOrderedLaunch& L = plan[l];
+        const WgradProblem* q = p + L.l.first;
+        WgradGroupArgs args;
+        WgradFoldArgs fargs;
+        int nblocks = 0, nfold = 0, slot = 0;
+        for (int k = 0; k < SS_WGRAD_GROUP_MAX; ++k) {
+            args.p[k] = WgradGroupItem{};
+            args.p[k].first = INT_MAX;
+            fargs.p[k] = WgradFoldItem{};
+            fargs.p[k].first = INT_MAX;
+        }
+        for (int k = 0; k < L.l.count; ++k) {
+            if (L.l.split[k] == 1) {
+                // one slice: the single-owner launch, no workspace
+                ss_wgrad_tn(q[k].dY, q[k].X, nullptr, q[k].gW, q[k].gb,
+                            q[k].Mo, q[k].N, q[k].Kb, 1, 0, stream);
+                continue;
+            }
+            float* const part = (float*)((char*)workspace + L.part_off[k]);
+            float* const partb =
+                q[k].gb ? (float*)((char*)workspace + L.partb_off[k])
+                        : nullptr;
+            WgradGroupItem& it = args.p[slot];
+            it.dY = (const __bf16*)q[k].dY;
+            it.X = (const __bf16*)q[k].X;
+            it.gW = part;
+            it.gb = partb;
+            it.Mo = q[k].Mo;
+            it.N = q[k].N;
+            it.Kb = q[k].Kb;
+            it.k_per_split = cdiv(cdiv(q[k].Kb, L.l.split[k]), 64) * 64;
+            it.gx = cdiv(q[k].Mo, L.cfg.bm);
+            it.gy = cdiv(q[k].N, L.cfg.bn);
+            it.first = nblocks;
+            nblocks += L.l.blocks[k];
+            WgradFoldItem& f = fargs.p[slot];
+            f.part = part;
+            f.partb = partb;
+            f.gW = (float*)q[k].gW;
+            f.gb = (float*)q[k].gb;
+            f.MN = (long)q[k].Mo * q[k].N;
+            f.Mo = q[k].Mo;
+            f.S = L.l.split[k];
+            f.first = nfold;
+            nfold += (int)((f.MN + 255) / 256) +
+                     (q[k].gb ? cdiv(q[k].Mo, 256) : 0);
+            ++slot;
+        }
+        if (!slot) continue;
+        if (L.cfg.bm == 128)
+            wgrad_group_part_launch<128, 128, WGRAD_KG_128>(nblocks, stream,
+                                                            args);
+        else if (L.cfg.bn == 128)
+            wgrad_group_part_launch<64, 128, WGRAD_KG_128>(nblocks, stream,
+                                                           args);
+        else
+            wgrad_group_part_launch<64, 64, WGRAD_KG_64>(nblocks, stream,
+                                                         args);
+        if (fold_waves == 4)
+            hipLaunchKernelGGL(wgrad_group_fold_kernel<4>, dim3(nfold),
+                               dim3(4 * 64), 0, stream, fargs);
+        else if (fold_waves == 8)
+            hipLaunchKernelGGL(wgrad_group_fold_kernel<8>, dim3(nfold),
+                               dim3(8 * 64), 0, stream, fargs);
+        else
+            hipLaunchKernelGGL(wgrad_group_fold_kernel<16>, dim3(nfold),
+                               dim3(16 * 64), 0, stream, fargs);
+    }
     return true;
 }

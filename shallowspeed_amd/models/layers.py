@@ -875,8 +875,10 @@ class Sequential(Module):
         """Backward of the head pair and the planned ReLU layers through
         ONE F.bwd_chain launch, then the unmasked wgrads in the
         per-layer order (head, then top to bottom): through one grouped
-        call (_wgrad_group), or one launch per layer in deterministic
-        mode, under deferred wgrad and with F.set_wgrad_group(False);
+        call (_wgrad_group; its ordered form in the deterministic
+        "grouped" wgrad mode), or one launch per layer in the other
+        deterministic modes, under deferred wgrad and with
+        F.set_wgrad_group(False);
         grad hooks fire after the launch that holds the layer.  Returns
         (True, dx of the lowest planned layer), or (False, None) with no
         stash touched when the tensors do not meet the kernel's contract.
@@ -923,9 +925,12 @@ class Sequential(Module):
             head._unstash("s", mubatch_id)
             lin._unstash("x", mubatch_id)
             heads, items = [lin], [(lin, dz_head, x, (head, lin))]
-        # deterministic mode keeps the single-owner kernel per layer,
-        # deferred wgrad keeps its chunks for the flush
-        grouped = F.wgrad_group_enabled() and not F.deterministic() \
+        # deterministic mode keeps one launch per layer except in its
+        # "grouped" wgrad mode (the ordered grouped launch), deferred
+        # wgrad keeps its chunks for the flush
+        ordered = F.deterministic() and F.deterministic_wgrad() == "grouped"
+        grouped = F.wgrad_group_enabled() \
+            and (ordered or not F.deterministic()) \
             and not any(l._defer_wgrad for l in heads + chain)
         if items and not grouped:
             self._wgrad_of(lin, dz_head, x)
@@ -945,10 +950,10 @@ class Sequential(Module):
             self._wgrad_of(layer, dz, xl)
             self._fire_grad_hooks(layer)
         if grouped:
-            self._wgrad_group(items)
+            self._wgrad_group(items, ordered)
         return True, dx
 
-    def _wgrad_group(self, items):
+    def _wgrad_group(self, items, ordered=False):
         """Weight gradients of `items`, (layer, dz, x, layers whose grad
         hooks follow), through F.linear_wgrad_group: same-tile layers
         share a launch.  Without grad hooks that is one call.  With
@@ -956,8 +961,10 @@ class Sequential(Module):
         hooks fire right after the launch that holds its gradient, in
         the per-layer order, so a later launch (the first layer's) is
         issued after the hooks of the layers before it and no bucket
-        waits on a wgrad it does not need."""
+        waits on a wgrad it does not need.  ordered: the
+        bitwise-reproducible form of the same launches, same cuts."""
         probs = [(dz, x, l.weight.grad, l.bias.grad) for l, dz, x, _ in items]
+        kw = {"ordered": True} if ordered else {}
         if not self._grad_hooks:
             cuts = [list(range(len(items)))]
         elif probs[0][0].is_cuda:
@@ -967,7 +974,7 @@ class Sequential(Module):
         else:
             cuts = [[k] for k in range(len(items))]
         for cut in cuts:
-            F.linear_wgrad_group([probs[k] for k in cut])
+            F.linear_wgrad_group([probs[k] for k in cut], **kw)
             for k in cut:
                 for hl in items[k][3]:
                     self._fire_grad_hooks(hl)

@@ -26,9 +26,9 @@ from ._ext import load_ext
 
 
 _DETERMINISTIC = False
-_DET_WGRAD = None      # "single" | "ordered"; None = the default below
+_DET_WGRAD = None      # one of _DET_WGRAD_MODES; None = the default below
 _DET_WGRAD_ENV = None  # SS_DET_WGRAD, read once
-_DET_WGRAD_MODES = ("single", "ordered")
+_DET_WGRAD_MODES = ("single", "ordered", "grouped")
 
 
 def set_deterministic(flag: bool, wgrad=None):
@@ -50,8 +50,14 @@ def set_deterministic(flag: bool, wgrad=None):
       "ordered"  split-K at full width: each slice's partial tile goes to
                  a workspace by plain stores and a second kernel adds the
                  partials in slice order (ext.wgrad_tn_ordered).
+      "grouped"  "ordered", with the weight gradients that follow the
+                 backward chain grouped as in the default path: per
+                 launch of the group plan one partial launch and one
+                 fold that adds a piece's slices in a fixed tree over
+                 the waves of a block (ext.wgrad_tn_group_ordered).
+                 Every other weight gradient is "ordered"'s.
       None       SS_DET_WGRAD (read once), else "single".
-    The two modes differ in f32 summation order, so in bits; each is a
+    The modes differ in f32 summation order, so in bits; each is a
     pure function of shapes and build."""
     global _DETERMINISTIC, _DET_WGRAD
     if wgrad is not None and wgrad not in _DET_WGRAD_MODES:
@@ -65,7 +71,7 @@ def deterministic() -> bool:
 
 
 def deterministic_wgrad() -> str:
-    """The deterministic mode's wgrad path, "single" or "ordered": what
+    """The deterministic mode's wgrad path, one of _DET_WGRAD_MODES: what
     the last set_deterministic named, else SS_DET_WGRAD, else "single"."""
     global _DET_WGRAD_ENV
     if _DET_WGRAD is not None:
@@ -343,7 +349,7 @@ def linear_wgrad_acc(dy, x, grad_w, grad_b=None, mask_src=None, split_k=0,
     Reference: functional.py:21 (dW = dout.T @ x, db = dout.sum(0)).
     """
     if split_k == 0 and _DETERMINISTIC:
-        if deterministic_wgrad() == "ordered":
+        if deterministic_wgrad() in ("ordered", "grouped"):
             ordered = True
         else:
             split_k = 1
@@ -398,16 +404,21 @@ def wgrad_group_plan(shapes, splits=None):
                 None if splits is None else [int(s) for s in splits])]
 
 
-def linear_wgrad_group(problems, splits=None):
+def linear_wgrad_group(problems, splits=None, ordered=False):
     """linear_wgrad_acc (unmasked) for each (dy, x, grad_w, grad_b) of
     `problems`, grad_b may be None.  On the GPU consecutive problems of
     one tile configuration run side by side in one launch; splits is
-    None or one value per problem, 0 (the launcher's rule) or >= 2."""
+    None or one value per problem, 0 (the launcher's rule) or >= 2.
+    ordered=True is the bitwise-reproducible form of the same launches
+    (set_deterministic's "grouped" mode): the problems' split-K partials
+    go to a workspace by plain stores and one fold per launch adds them
+    in a fixed order (ext.wgrad_tn_group_ordered)."""
     problems = list(problems)
     if not problems:
         return
     if _is_gpu(problems[0][0]):
-        load_ext(required=True).wgrad_tn_group(
+        ext = load_ext(required=True)
+        (ext.wgrad_tn_group_ordered if ordered else ext.wgrad_tn_group)(
             [tuple(p) for p in problems],
             None if splits is None else [int(s) for s in splits])
         return
@@ -998,7 +1009,7 @@ def linear_wgrad_multi(chunks, grad_w, grad_b=None, split_k=0):
         # (split_k=0) keeps the single fused launch.
         # In the "ordered" deterministic mode each chunk is an ordered
         # split-K call (the caller's split_k = 0), chunks in call order.
-        if _DETERMINISTIC and deterministic_wgrad() == "ordered" \
+        if _DETERMINISTIC and deterministic_wgrad() != "single" \
                 and forced:
             split_k = 0
         for dy, x, m in chunks:

@@ -107,13 +107,15 @@ def main():
                          "(forces the single-owner split_k=1 wgrad path, or "
                          "the one --deterministic-wgrad names; "
                          "bucket reduction order is fixed by construction)")
-    ap.add_argument("--deterministic-wgrad", choices=["single", "ordered"],
-                    default=None,
+    ap.add_argument("--deterministic-wgrad",
+                    choices=["single", "ordered", "grouped"], default=None,
                     help="with --deterministic: single = one block per "
                          "output tile walks the whole batch; ordered = "
                          "split-K partials to a workspace, folded in slice "
-                         "order (full width).  Default: SS_DET_WGRAD, else "
-                         "single")
+                         "order (full width); grouped = ordered, with the "
+                         "layers after the backward chain sharing one "
+                         "partial launch and one tree fold.  Default: "
+                         "SS_DET_WGRAD, else single")
     ap.add_argument("--fp8-fwd", action="store_true",
                     help="MX-fp8 training forward on qualifying Linears "
                          "(O%%256,I%%256,µbatch%%256); backward stays bf16, "
