@@ -1029,6 +1029,62 @@ torch::Tensor fused_mlp_argmax(torch::Tensor x, torch::Tensor desc,
     return out;
 }
 
+// The wide fused serving forward (fused_mlp_wide.hip): ws / bs are the
+// Linear layers bottom first, hidden ones then the head; H, nhidden, cout
+// and in_dim are read from them.  Returns (argmax int32 [M], logits f32
+// [M][cout]), logits an empty tensor unless asked for.  Raises, with
+// nothing allocated or launched, outside the kernel's contract.  rows /
+// waves: 0 = the shipped arm.
+std::vector<torch::Tensor> fused_mlp_fwd(torch::Tensor x,
+                                         std::vector<torch::Tensor> ws,
+                                         std::vector<torch::Tensor> bs,
+                                         bool want_logits, int64_t rows,
+                                         int64_t waves) {
+    check_bf16(x, "x");
+    const int64_t n = (int64_t)ws.size();
+    TORCH_CHECK(n >= 2 && n <= SS_FUSED_MLP_MAX + 1 && (int64_t)bs.size() == n,
+                "fused_mlp_fwd takes 1..", SS_FUSED_MLP_MAX,
+                " hidden layers and a head, with one bias each");
+    TORCH_CHECK(x.dim() == 2 && x.size(0) >= 1 && x.size(1) >= 1 &&
+                    x.size(0) <= INT_MAX - 64 && x.size(1) <= INT_MAX / 2,
+                "x must be [M][in_dim], M and in_dim >= 1");
+    const int64_t M = x.size(0), K0 = x.size(1);
+    TORCH_CHECK(ws[0].dim() == 2, "weights must be 2-D");
+    const int64_t H = ws[0].size(0), C = ws[n - 1].dim() == 2
+                                             ? ws[n - 1].size(0) : 0;
+    TORCH_CHECK(H == 128 || H == 256 || H == 512 || H == 1024,
+                "hidden width must be 128, 256, 512 or 1024, is ", H);
+    TORCH_CHECK(C >= 1 && C <= 16, "head width must be 1..16, is ", C);
+    const void* wp[SS_FUSED_MLP_MAX + 1] = {};
+    const void* bp[SS_FUSED_MLP_MAX + 1] = {};
+    for (int64_t l = 0; l < n; ++l) {
+        check_bf16(ws[l], "w");
+        check_bf16(bs[l], "b");
+        TORCH_CHECK(ws[l].device() == x.device() &&
+                        bs[l].device() == x.device(),
+                    "x, weights and biases must share a device");
+        TORCH_CHECK(ws[l].dim() == 2 && ws[l].size(0) == (l == n - 1 ? C : H) &&
+                        ws[l].size(1) == (l == 0 ? K0 : H) &&
+                        bs[l].numel() == ws[l].size(0),
+                    "layer ", l, ": shape outside in_dim -> H x nhidden -> cout");
+        TORCH_CHECK(aligned16(ws[l].data_ptr()), "layer ", l,
+                    ": weight must be 16-byte aligned");
+        wp[l] = ws[l].data_ptr();
+        bp[l] = bs[l].data_ptr();
+    }
+    auto amax = torch::empty({M}, x.options().dtype(torch::kInt32));
+    auto logits = torch::empty({want_logits ? M : 0, C},
+                               x.options().dtype(torch::kFloat));
+    TORCH_CHECK(ss_fused_mlp_wide(x.data_ptr(), wp, bp, (int)(n - 1),
+                                  wp[n - 1], bp[n - 1], amax.data_ptr(),
+                                  want_logits ? logits.data_ptr() : nullptr,
+                                  (int)M, (int)K0, (int)H, (int)C, (int)rows,
+                                  (int)waves, cur_stream()),
+                "fused_mlp_fwd: no arm (rows, waves) = (", rows, ", ", waves,
+                ") for H = ", H);
+    return {amax, logits};
+}
+
 void transpose_bf16(torch::Tensor src, torch::Tensor dst) {
     check_bf16(src, "src");
     check_bf16(dst, "dst");
@@ -1158,6 +1214,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("adamw_multi2", &adamw_multi2);
     m.def("fused_mlp_argmax", &fused_mlp_argmax,
           "persistent fused MLP forward + per-row argmax (serving)");
+    m.def("fused_mlp_fwd", &fused_mlp_fwd,
+          "fused serving forward, H in {128, 256, 512, 1024}, any batch -> "
+          "(argmax, f32 logits or empty); raises outside the contract",
+          py::arg("x"), py::arg("ws"), py::arg("bs"),
+          py::arg("want_logits") = false, py::arg("rows") = 0,
+          py::arg("waves") = 0);
     m.def("ln_fwd", &ln_fwd);
     m.def("ln_bwd_dx", &ln_bwd_dx);
     m.def("ln_bwd_dparam", &ln_bwd_dparam);

@@ -214,6 +214,22 @@ bool ss_fwd_chain_stage(const void* x, const void* const* w,
 bool ss_fused_mlp_fwd(const void* x, const void* desc, int M, int in_dim,
                       int nhidden, int cout, void* out, hipStream_t stream);
 
+// ---- fused_mlp_wide.hip
+// The whole serving forward in one launch for H in {128, 256, 512, 1024}:
+// x [M][in_dim] -> H (ReLU) x nhidden -> cout, any M >= 1, any
+// in_dim >= 1, 1 <= nhidden <= SS_FUSED_MLP_MAX, 1 <= cout <= 16.
+// w / b: nhidden pointers each, bottom layer first (W [H][in], bf16
+// bias); w_head [cout][H].  Weights 16-byte aligned.  argmax: int32 [M],
+// the lowest index among equal maxima; logits: f32 [M][cout], the values
+// the argmax is taken over, or null.  rows / waves: 0 = the shipped
+// choice, else one of the arms built for H.
+constexpr int SS_FUSED_MLP_MAX = 8;
+bool ss_fused_mlp_wide(const void* x, const void* const* w,
+                       const void* const* b, int nhidden, const void* w_head,
+                       const void* b_head, void* argmax, void* logits, int M,
+                       int in_dim, int H, int cout, int rows, int waves,
+                       hipStream_t stream);
+
 // ---- elementwise.hip
 void ss_relu_fwd(const void* x, void* y, long n, hipStream_t stream);
 void ss_relu_bwd(const void* dy, const void* y, void* dx, long n,

@@ -81,6 +81,40 @@ def build_fused_plan(model, batch):
     return (desc, ls[0].in_dims, len(hidden), head.out_dims)
 
 
+def fused_forward_fn(model, batch, scores=False):
+    """How --fused runs a batch of `batch` rows of this model: a callable
+    x -> argmax (x -> (argmax, f32 logits) with scores=True), or None
+    when no fused kernel serves the model.
+
+    The 256-wide flagship at batch % 64 == 0 keeps csrc/fused_mlp.hip
+    (build_fused_plan); every other ReLU chain of one hidden width in
+    {128, 256, 512, 1024} with a head of up to 16 classes, at any batch,
+    and any request for scores, goes to csrc/fused_mlp_wide.hip through
+    F.fused_mlp_forward."""
+    from shallowspeed_amd.models import Linear
+    from shallowspeed_amd.ops import functional as F
+    from shallowspeed_amd.ops import load_ext
+
+    if model.device.type != "cuda":
+        return None
+    plan = None if scores else build_fused_plan(model, batch)
+    if plan is not None:
+        ext = load_ext(required=True)
+        desc, ind, nh, co = plan
+        return lambda x: ext.fused_mlp_argmax(x, desc, ind, nh, co)
+    ls = [l for l in model.layers if isinstance(l, Linear)]
+    if len(ls) < 2 or ls[-1].activation is not None or any(
+            l.activation != "relu" for l in ls[:-1]):
+        return None
+    ws = [l.weight.compute() for l in ls]
+    bs = [l.bias.compute() for l in ls]
+    probe = torch.zeros(1, ls[0].in_dims, dtype=torch.bfloat16,
+                        device=model.device)
+    if not F.fused_mlp_ok(probe, ws, bs):
+        return None
+    return lambda x: F.fused_mlp_forward(x, ws, bs, logits=scores)
+
+
 def fp8_forward(plan, x):
     """fp8-RESIDENT chain: a layer whose successor is also fp8 emits
     its output pre-quantized from the GEMM epilogue (gemm_nt_f8_q) —
@@ -125,8 +159,13 @@ def main():
     ap.add_argument("--fused", action="store_true",
                     help="persistent fused-MLP forward kernel (whole "
                          "layer chain in ONE launch, LDS-resident "
-                         "activations, in-kernel argmax; 256-wide "
-                         "hidden chains)")
+                         "activations, in-kernel argmax; ReLU chains "
+                         "of one hidden width in 128/256/512/1024, "
+                         "up to 8 hidden layers and 16 classes, any "
+                         "batch)")
+    ap.add_argument("--scores", default=None, metavar="PATH",
+                    help="with --fused: also save the f32 logits the "
+                         "argmax was taken over (.pt)")
     ap.add_argument("--graph", action="store_true",
                     help="capture the forward-only batch in a hipGraph "
                          "and replay it per batch (single GPU; collapses "
@@ -161,16 +200,19 @@ def main():
         assert args.pp == 1, "--fp8 serving path is single-stage"
         fp8_plan = build_fp8_plan(model, args.batch)
 
-    fused_plan = None
+    fused_fn = None
     if args.fused and topo.world == 1 and not fp8_plan:
-        fused_plan = build_fused_plan(model, args.batch)
-        if fused_plan is None:
+        fused_fn = fused_forward_fn(model, args.batch,
+                                    scores=bool(args.scores))
+        if fused_fn is None:
             print("# --fused: model/batch outside the fused tier, "
                   "falling back", flush=True)
+    if args.scores and fused_fn is None:
+        print("# --scores needs the --fused path: not written", flush=True)
 
     graphed = None
     if args.graph and device.type == "cuda" and topo.world == 1 \
-            and not fp8_plan and fused_plan is None:
+            and not fp8_plan and fused_fn is None:
         # Serving graph: one persistent input slot + captured forward
         # + argmax; per batch = one D2D copy + one graph replay.  The
         # forward-only loop is launch-gap-bound (kernel sum ~59 µs vs
@@ -202,16 +244,14 @@ def main():
     t0 = time.perf_counter()
     from shallowspeed_amd.ops.functional import row_argmax
 
-    if fused_plan is not None:
-        from shallowspeed_amd.ops import load_ext
-
-        _e = load_ext(required=True)
-
+    scores = []
     for b in range(ds.num_batches()):
-        if fused_plan is not None:
-            desc, ind, nh, co = fused_plan
-            xb = ds.x_compute[b * args.batch:(b + 1) * args.batch]
-            preds.append(_e.fused_mlp_argmax(xb, desc, ind, nh, co))
+        if fused_fn is not None:
+            out = fused_fn(ds.x_compute[b * args.batch:(b + 1) * args.batch])
+            if args.scores:
+                scores.append(out[1])
+                out = out[0]
+            preds.append(out)
             continue
         if graphed is not None:
             g, gx, gout = graphed
@@ -246,6 +286,9 @@ def main():
         if args.out:
             torch.save(torch.cat(preds), args.out)
             print(f"predictions -> {args.out}")
+        if scores:
+            torch.save(torch.cat([s.cpu() for s in scores]), args.scores)
+            print(f"scores -> {args.scores}")
 
 
 if __name__ == "__main__":

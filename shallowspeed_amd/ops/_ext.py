@@ -87,6 +87,7 @@ def build_ext(verbose=True):
         os.path.join(src_dir, "fwd_chain_stage.hip"),
         os.path.join(src_dir, "norm.hip"),
         os.path.join(src_dir, "fused_mlp.hip"),
+        os.path.join(src_dir, "fused_mlp_wide.hip"),
     ]
     mod = load(
         name=_EXT_NAME,

@@ -1061,3 +1061,73 @@ def row_argmax(x):
     if _is_gpu(x) and x.dtype == torch.bfloat16:
         return _ext_for(x).row_argmax(x).long()
     return x.argmax(dim=-1)
+
+
+# ------------------------------------------------- fused serving forward
+
+# width -> the (rows, waves) arms csrc/fused_mlp_wide.hip is built for
+FUSED_MLP_ARMS = {128: ((32, 4), (64, 4)), 256: ((32, 4), (64, 4), (64, 8)),
+                  512: ((32, 8), (64, 8), (64, 16)),
+                  1024: ((32, 8), (32, 16), (64, 8))}
+_FUSED_DESC = OrderedDict()  # pointer tuple -> device table of the 256 kernel
+
+
+def fused_mlp_ok(x, ws, bs):
+    """The contract of csrc/fused_mlp_wide.hip, from the tensors alone."""
+    n = len(ws)
+    if n < 2 or n > 9 or len(bs) != n:
+        return False
+    ts = [x, *ws, *bs]
+    if not all(torch.is_tensor(t) and t.is_cuda and t.is_contiguous()
+               and t.dtype == torch.bfloat16 and t.device == x.device
+               for t in ts):
+        return False
+    if x.dim() != 2 or x.shape[0] < 1 or x.shape[1] < 1:
+        return False
+    if any(w.dim() != 2 or w.data_ptr() % 16 for w in ws):
+        return False
+    H, C = ws[0].shape[0], ws[-1].shape[0]
+    if H not in FUSED_MLP_ARMS or not 1 <= C <= 16:
+        return False
+    return all(tuple(w.shape) == (C if l == n - 1 else H,
+                                  x.shape[1] if l == 0 else H)
+               and b.numel() == w.shape[0]
+               for l, (w, b) in enumerate(zip(ws, bs)))
+
+
+def fused_mlp_forward(x, ws, bs, logits=False, rows=0, waves=0):
+    """The whole serving forward in one kernel (GPU only).
+
+    ws / bs: weights and biases of the Linear layers, bottom first: 1..8
+    hidden layers (H, in) with ReLU, H in {128, 256, 512, 1024}, then the
+    head (cout <= 16, H).  x: (M, in_dim) bf16, any M >= 1, any in_dim.
+
+      h_l = bf16(relu(h_{l-1} @ W_l^T + b_l)) ; z = h @ W_head^T + b_head
+
+    Returns the int32 row argmax of z (the lowest index among equal
+    maxima), or (argmax, z) with z as the unrounded f32 (M, cout) the
+    argmax was taken over when logits=True.  None, with nothing launched,
+    for CPU tensors or shapes outside the contract (the caller takes the
+    per-layer path).
+
+    H = 256 with M % 64 == 0 and no logits runs csrc/fused_mlp.hip, as
+    before; everything else csrc/fused_mlp_wide.hip, where rows / waves
+    select a measured arm (0: the shipped choice)."""
+    ws, bs = list(ws), list(bs)
+    if not fused_mlp_ok(x, ws, bs):
+        return None
+    ext = _ext_for(x)
+    M, H = x.shape[0], ws[0].shape[0]
+    if H == 256 and M % 64 == 0 and not logits and not rows and not waves:
+        ptrs = tuple(p for w, b in zip(ws, bs)
+                     for p in (w.data_ptr(), b.data_ptr()))
+        desc = _FUSED_DESC.get((x.device, ptrs))
+        if desc is None:
+            desc = torch.tensor(ptrs, dtype=torch.int64).to(x.device)
+            _FUSED_DESC[(x.device, ptrs)] = desc
+            if len(_FUSED_DESC) > 16:
+                _FUSED_DESC.popitem(last=False)
+        return ext.fused_mlp_argmax(x, desc, x.shape[1], len(ws) - 1,
+                                    ws[-1].shape[0])
+    amax, z = ext.fused_mlp_fwd(x, ws, bs, bool(logits), int(rows), int(waves))
+    return (amax, z) if logits else amax
