@@ -879,6 +879,84 @@ std::vector<torch::Tensor> fwd_chain_stage(torch::Tensor x,
                          std::nullopt);
 }
 
+// Wide forward chain (fwd_chain_wide.hip): fwd_chain at H = 128 or 512,
+// H read from w_head.  The first layer always streams x.  Returns
+// [h_0, ..., h_{n-1}, probs], or an EMPTY list with nothing allocated or
+// launched outside the kernel's contract.
+std::vector<torch::Tensor> fwd_chain_wide(torch::Tensor x,
+                                          std::vector<torch::Tensor> ws,
+                                          std::vector<torch::Tensor> bs,
+                                          torch::Tensor w_head,
+                                          torch::Tensor b_head, int64_t rows,
+                                          int64_t waves) {
+    const int64_t n = (int64_t)ws.size();
+    if (n < 1 || n > SS_FWD_CHAIN_MAX || (int64_t)bs.size() != n) return {};
+    if (!plain(x, 2) || !plain(w_head, 2) || !plain(b_head, 1)) return {};
+    const int64_t M = x.size(0), K0 = x.size(1);
+    const int64_t C = w_head.size(0), H = w_head.size(1);
+    if (M > INT_MAX / 1024 || K0 % 8 != 0 || C > 16 || b_head.numel() != C ||
+        !ss_chain_wide_arm_built((int)H, (int)rows, (int)waves))
+        return {};
+    const void* wp[SS_FWD_CHAIN_MAX] = {};
+    const void* bp[SS_FWD_CHAIN_MAX] = {};
+    void* hp[SS_FWD_CHAIN_MAX] = {};
+    for (int64_t l = 0; l < n; ++l) {
+        if (!plain(ws[l], 2) || !plain(bs[l], 1) || ws[l].size(0) != H ||
+            ws[l].size(1) != (l == 0 ? K0 : H) || bs[l].numel() != H)
+            return {};
+        wp[l] = ws[l].data_ptr();
+        bp[l] = bs[l].data_ptr();
+    }
+    std::vector<torch::Tensor> out;
+    for (int64_t l = 0; l < n; ++l) {
+        out.push_back(torch::empty({M, H}, x.options()));
+        hp[l] = out.back().data_ptr();
+    }
+    out.push_back(torch::empty({M, C}, x.options()));
+    if (!ss_fwd_chain_wide(x.data_ptr(), wp, bp, hp, (int)n,
+                           w_head.data_ptr(), b_head.data_ptr(),
+                           out.back().data_ptr(), (int)M, (int)K0, (int)H,
+                           (int)C, (int)rows, (int)waves, cur_stream()))
+        return {};
+    return out;
+}
+
+// Wide backward chain (bwd_chain_wide.hip): bwd_chain at H = 128 or 512,
+// H read from w_head_t.  Returns [dz_head, dz_0, ..., dz_{n-1}(, dx)], or
+// an EMPTY list with nothing allocated or launched.
+std::vector<torch::Tensor> bwd_chain_wide(torch::Tensor probs,
+                                          torch::Tensor target,
+                                          torch::Tensor w_head_t,
+                                          double global_batch,
+                                          std::vector<torch::Tensor> hs,
+                                          std::vector<torch::Tensor> w_ts,
+                                          int64_t rows, int64_t waves) {
+    const int64_t n = (int64_t)hs.size();
+    const int64_t nw = (int64_t)w_ts.size();
+    if (n < 1 || n > SS_BWD_CHAIN_MAX || (nw != n && nw != n - 1)) return {};
+    if (!plain(probs, 2) || !plain(target, 2) || !plain(w_head_t, 2))
+        return {};
+    if (probs.sizes() != target.sizes()) return {};
+    const int64_t M = probs.size(0), C = probs.size(1), H = w_head_t.size(0);
+    if (M > INT_MAX / 1024 || C > 16 || w_head_t.size(1) != C ||
+        !ss_chain_wide_arm_built((int)H, (int)rows, (int)waves))
+        return {};
+    const void* hp[SS_BWD_CHAIN_MAX] = {};
+    const void* wp[SS_BWD_CHAIN_MAX] = {};
+    void* dp[SS_BWD_CHAIN_MAX] = {};
+    if (!bwd_chain_operands(hs, w_ts, M, H, hp, wp)) return {};
+    std::vector<torch::Tensor> out;
+    out.push_back(torch::empty_like(probs));
+    void* dx_p = bwd_chain_outputs(hs, nw == n, out, dp);
+    if (!ss_bwd_chain_wide(probs.data_ptr(), target.data_ptr(),
+                           w_head_t.data_ptr(), out[0].data_ptr(), hp, wp, dp,
+                           (int)n, dx_p, (int)M, (int)H, (int)C,
+                           (float)(1.0 / global_batch), (int)rows, (int)waves,
+                           cur_stream()))
+        return {};
+    return out;
+}
+
 // Adds the metric totals of (probs, target) into acc: loss_sum (kind
 // "xent" or "mse"), argmax matches, rows, non-finite rows.
 void head_metrics(torch::Tensor probs, torch::Tensor target,
@@ -1203,6 +1281,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           py::arg("dout"), py::arg("hs"), py::arg("w_ts"),
           py::arg("rows") = 0, py::arg("waves") = 0, py::arg("w_lds") = 0,
           py::arg("dz_scale") = 1.0);
+    m.def("fwd_chain_wide", &fwd_chain_wide,
+          "H-wide ReLU layers (H = 128 or 512) + fused head forward in one "
+          "launch -> [h_l..., probs], or [] outside the contract",
+          py::arg("x"), py::arg("ws"), py::arg("bs"), py::arg("w_head"),
+          py::arg("b_head"), py::arg("rows") = 0, py::arg("waves") = 0);
+    m.def("bwd_chain_wide", &bwd_chain_wide,
+          "head backward + H-wide ReLU dgrads (H = 128 or 512) in one launch "
+          "-> [dz_head, dz_l..., (dx)], or [] outside the contract",
+          py::arg("probs"), py::arg("target"), py::arg("w_head_t"),
+          py::arg("global_batch"), py::arg("hs"), py::arg("w_ts"),
+          py::arg("rows") = 0, py::arg("waves") = 0);
     m.def("head_metrics", &head_metrics,
           "metric totals of (probs, target) into a slotted accumulator",
           py::arg("probs"), py::arg("target"), py::arg("acc"),

@@ -210,6 +210,29 @@ bool ss_fwd_chain_stage(const void* x, const void* const* w,
                         int M, int K0, int H, int rows, int waves, int l1,
                         int kloop, hipStream_t stream);
 
+// ---- fwd_chain_wide.hip / bwd_chain_wide.hip
+// The headed chains at H = 128 and 512, with ss_fwd_chain's and
+// ss_bwd_chain's pointer lists.  The first layer always streams x (any
+// K0 % 8 == 0, K0 == H included).  rows / waves: both 0 = the shipped
+// arm of (H, M), else one of the pairs built for H: (32, 4), (64, 4) at
+// 128; (32, 8), (64, 8), (64, 16) at 512.  No zeroing, no dropout scale,
+// no W-through-LDS arm.
+// Host only: whether (rows, waves) selects an arm built for H (both 0
+// does, at H = 128 and 512), so that a caller can refuse before it
+// allocates.
+bool ss_chain_wide_arm_built(int H, int rows, int waves);
+bool ss_fwd_chain_wide(const void* x, const void* const* w,
+                       const void* const* b, void* const* h, int nlayers,
+                       const void* W_head, const void* b_head, void* probs,
+                       int M, int K0, int H, int C, int rows, int waves,
+                       hipStream_t stream);
+bool ss_bwd_chain_wide(const void* probs, const void* target,
+                       const void* Wt_head, void* dz_head,
+                       const void* const* h, const void* const* wt,
+                       void* const* dz, int nlayers, void* dx, int M, int H,
+                       int C, float inv_gb, int rows, int waves,
+                       hipStream_t stream);
+
 // ---- fused_mlp.hip
 bool ss_fused_mlp_fwd(const void* x, const void* desc, int M, int in_dim,
                       int nhidden, int cout, void* out, hipStream_t stream);

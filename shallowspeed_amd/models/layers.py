@@ -626,12 +626,14 @@ class Sequential(Module):
             return None
         return pair
 
-    def _chain_run(self, top=None):
+    def _chain_run(self, top=None, width=None):
         """Indices, top first, of the consecutive Linear(activation=
-        "relu") layers with out_dims == 256 from layer `top` down
-        (default: right under the head pair), at most
+        "relu") layers with out_dims == width (default 256) from layer
+        `top` down (default: right under the head pair), at most
         _CHAIN_MAX_LAYERS.  A chain plan is a prefix of it."""
         run = []
+        if width is None:
+            width = self._CHAIN_WIDTH
         if top is None:
             top = len(self.layers) - 3
         for i in range(top, -1, -1):
@@ -639,7 +641,7 @@ class Sequential(Module):
             if len(run) == self._CHAIN_MAX_LAYERS \
                     or type(layer) is not Linear \
                     or layer.activation != "relu" \
-                    or layer.out_dims != self._CHAIN_WIDTH:
+                    or layer.out_dims != width:
                 break
             run.append(i)
         return run
@@ -686,14 +688,78 @@ class Sequential(Module):
             return None
         return self._fwd_chain_plan(top=len(self.layers) - 1)
 
-    def _forward_chain(self, plan, lin, head, x, mubatch_id):
+    def _wide_head_width(self, rows=None):
+        """in_dims of the head pair's Linear when the wide chain kernels
+        (F.fwd_chain_wide / F.bwd_chain_wide) run under it at `rows`
+        micro-batch rows (None: at some batch): F.chain_wide_planned, the fused head on and its wgrad not riding in
+        head_bwd_fused, H in F.CHAIN_WIDE_WIDTHS, C <= 16, no fp8
+        forward.  Else None."""
+        pair = self._head_pair()
+        if not F.head_fused() or F.head_wgrad_fused() or pair is None \
+                or pair[0].in_dims not in F.CHAIN_WIDE_WIDTHS \
+                or pair[0].out_dims > 16 or pair[0].fp8_fwd \
+                or not F.chain_wide_planned(pair[0].in_dims, rows):
+            return None
+        return pair[0].in_dims
+
+    def _fwd_wide_plan(self, rows=None):
+        """_fwd_chain_plan at width H = 128 or 512 (the head Linear's
+        in_dims), for F.fwd_chain_wide: the run of Linear(activation=
+        "relu") layers with out_dims == H right under the fused head, at
+        most eight.  A layer is in the chain when in_dims == H, or when
+        it ends the run and in_dims % 8 == 0 (the kernel streams the
+        input of its first layer).  None with dropout or an fp8 forward
+        on a layer it would take.  Consulted only where
+        _fwd_chain_plan() is None; width 256 is that plan's.  rows: the
+        micro-batch rows, where the caller knows them."""
+        width = self._wide_head_width(rows)
+        if width is None:
+            return None
+        plan = []
+        for i in self._chain_run(width=width):
+            layer = self.layers[i]
+            streamed = layer.in_dims != width
+            if streamed and (layer.in_dims < 8 or layer.in_dims % 8 != 0):
+                break
+            if layer.dropout > 0.0 or layer.fp8_fwd:
+                return None
+            plan.append(i)
+            if streamed:
+                break
+        return plan[::-1] or None
+
+    def _bwd_wide_plan(self, mubatch_rows: int = 1):
+        """_bwd_chain_plan at width H = 128 or 512, for F.bwd_chain_wide:
+        (layer index, dgrad_in_chain), top layer first.  A layer's dgrad
+        is in the chain when in_dims == H and its dx is needed; the
+        chain ends with the first layer whose dgrad is not (that layer
+        still gets its dz from the kernel).  None with dropout on a
+        planned layer (the kernel has no dz scale).  Consulted only
+        where _bwd_chain_plan() is None."""
+        width = self._wide_head_width(mubatch_rows)
+        if width is None or mubatch_rows < 1:
+            return None
+        plan = []
+        for i in self._chain_run(width=width):
+            layer = self.layers[i]
+            if layer.dropout > 0.0:
+                return None
+            need_dx = not (i == 0 and self._skip_input_grad)
+            in_chain = need_dx and layer.in_dims == width
+            plan.append((i, in_chain))
+            if not in_chain:
+                break
+        return plan or None
+
+    def _forward_chain(self, plan, lin, head, x, mubatch_id, launch=None):
         """Forward of the planned ReLU layers and the head pair through
         ONE F.fwd_chain launch, leaving the stashes the layers' own
         forwards leave.  Returns probs, or None with no stash touched
         when the tensors do not meet the kernel's contract.  lin = head
         = None (a stage plan): ONE F.fwd_chain_stage launch, which never
         takes a deferred zero_grad along; returns the top layer's
-        output."""
+        output.  launch (a wide plan): F.fwd_chain_wide in place of
+        F.fwd_chain, which takes no deferred zero_grad along either."""
         chain = [self.layers[i] for i in plan]
         if lin is None:
             hs = F.fwd_chain_stage(x, [l.weight.compute() for l in chain],
@@ -711,10 +777,10 @@ class Sequential(Module):
         # of every kernel that adds to the gradients)
         zero = self._flat_grad if getattr(self, "_zero_pending", False) \
             and self._flat_grad.device == x.device else None
-        res = F.fwd_chain(x, [l.weight.compute() for l in chain],
-                          [l.bias.compute() for l in chain],
-                          lin.weight.compute(), lin.bias.compute(),
-                          zero=zero)
+        args = (x, [l.weight.compute() for l in chain],
+                [l.bias.compute() for l in chain],
+                lin.weight.compute(), lin.bias.compute())
+        res = launch(*args) if launch else F.fwd_chain(*args, zero=zero)
         if res is None:
             return None
         if zero is not None:
@@ -733,17 +799,22 @@ class Sequential(Module):
         pair = self._head_pair()
         n_plain = len(self.layers) - 2 if pair else len(self.layers)
         plan = None
+        wide = None
         if inputs.is_cuda:
             plan = self._fwd_chain_plan() if pair else self._fwd_stage_plan()
+            if plan is None and pair:
+                plan = self._fwd_wide_plan(inputs.shape[0])
+                wide = F.fwd_chain_wide if plan else None
         if plan:
-            if not pair:
-                # the stage launch takes no deferred zero_grad along
+            if not pair or wide:
+                # the stage and the wide launch take no deferred
+                # zero_grad along
                 self._settle_zero_grad()
             # layers below the chain run their own forward first
             for layer in self.layers[:plan[0]]:
                 x = layer.forward(x, mubatch_id)
             s = self._forward_chain(plan, *(pair or (None, None)), x,
-                                    mubatch_id)
+                                    mubatch_id, wide)
             if s is not None:
                 return s
             first = plan[0]
@@ -871,7 +942,8 @@ class Sequential(Module):
         else:
             F.linear_wgrad_acc(dz, x, layer.weight.grad, layer.bias.grad)
 
-    def _backward_chain(self, plan, lin, head, target, mubatch_id):
+    def _backward_chain(self, plan, lin, head, target, mubatch_id,
+                        launch=None):
         """Backward of the head pair and the planned ReLU layers through
         ONE F.bwd_chain launch, then the unmasked wgrads in the
         per-layer order (head, then top to bottom): through one grouped
@@ -885,7 +957,9 @@ class Sequential(Module):
 
         lin = head = None (a stage plan): `target` is the gradient the
         stage received, and the launch is ONE F.bwd_chain_stage on it;
-        the wgrads follow in the same way."""
+        the wgrads follow in the same way.  launch (a wide plan):
+        F.bwd_chain_wide in place of F.bwd_chain; everything after the
+        launch is the same."""
         chain = [self.layers[i] for i, _ in plan]
         hs = [l._cache.get(("y", mubatch_id)) for l in chain]
         if lin is None:
@@ -911,9 +985,10 @@ class Sequential(Module):
                 target = target.contiguous()
             w_ts = [l.weight.compute_t()
                     for l, (_, dg) in zip(chain, plan) if dg]
-            res = F.bwd_chain(s, target, lin.weight.compute_t(),
-                              head.global_batch_size, hs, w_ts,
-                              dz_scale=chain[0].dz_scale())
+            args = (s, target, lin.weight.compute_t(),
+                    head.global_batch_size, hs, w_ts)
+            res = launch(*args) if launch else \
+                F.bwd_chain(*args, dz_scale=chain[0].dz_scale())
             if res is None:
                 return False, None
             dz_head, dzs, dx = res
@@ -984,13 +1059,16 @@ class Sequential(Module):
         d = dout
         last = len(self.layers) - 1
         pair = self._head_pair()
-        plan = None
+        plan = wide = None
         if dout.is_cuda:
             plan = self._bwd_chain_plan(dout.shape[0]) if pair \
                 else self._bwd_stage_plan(dout.shape[0])
+            if plan is None and pair:
+                plan = self._bwd_wide_plan(dout.shape[0])
+                wide = F.bwd_chain_wide if plan else None
         if plan:
             ok, dx = self._backward_chain(plan, *(pair or (None, None)), d,
-                                          mubatch_id)
+                                          mubatch_id, wide)
             if ok:
                 d = dx
                 last = plan[-1][0] - 1

@@ -194,6 +194,61 @@ def fwd_chain_enabled() -> bool:
     return _FWD_CHAIN
 
 
+_CHAIN_WIDE = None
+CHAIN_WIDE_WIDTHS = (128, 512)
+# (rows, waves) arms the wide chain kernels are built with, per width
+CHAIN_WIDE_ARMS = {128: ((32, 4), (64, 4)),
+                   512: ((32, 8), (64, 8), (64, 16))}
+
+
+def set_chain_wide(flag: bool):
+    """Run the forward and the backward of a model whose ReLU layers
+    under the fused head are 128 or 512 wide as the chain kernels of
+    csrc/fwd_chain_wide.hip and csrc/bwd_chain_wide.hip (see
+    fwd_chain_wide / bwd_chain_wide; width 256 keeps fwd_chain /
+    bwd_chain).  Every h_l, probs, dz and dx keeps its bits.  One switch
+    for both: True plans them at every batch, False never;
+    SS_CHAIN_WIDE=1 / 0 (read once) does the same.  Left alone, they are
+    planned where they were measured to win: chain_wide_planned."""
+    global _CHAIN_WIDE
+    _CHAIN_WIDE = bool(flag)
+
+
+def _chain_wide_mode():
+    """True / False as switched; "auto" when nobody has switched."""
+    global _CHAIN_WIDE
+    if _CHAIN_WIDE is None:
+        import os
+
+        _CHAIN_WIDE = {"1": True, "0": False}.get(
+            os.environ.get("SS_CHAIN_WIDE"), "auto")
+    return _CHAIN_WIDE
+
+
+def chain_wide_enabled() -> bool:
+    """Whether the wide chains are not switched off."""
+    return _chain_wide_mode() is not False
+
+
+# Micro-batch rows from which the wide chains are planned when nobody has
+# switched them: where a step beat the per-layer path by more than five
+# times its run-to-run spread (profiles/r20_chain_wide.md).  H = 512 wins
+# at 16384 rows (0.229 against 0.284 ms) and loses at 1024 (0.147 against
+# 0.136); H = 128 wins at 1024 and loses at 16384, and stays unplanned
+# until the batch at which it turns is measured.
+CHAIN_WIDE_MIN_ROWS = {512: 16384}
+
+
+def chain_wide_planned(width, rows=None) -> bool:
+    """Whether a model of hidden width `width` takes the wide chains at
+    `rows` micro-batch rows (None: at some batch)."""
+    mode = _chain_wide_mode()
+    if mode != "auto":
+        return mode
+    return width in CHAIN_WIDE_MIN_ROWS and (
+        rows is None or rows >= CHAIN_WIDE_MIN_ROWS[width])
+
+
 _FWD_CHAIN_L1 = None
 
 
@@ -817,6 +872,50 @@ def bwd_chain_stage(dout, hs, w_ts, rows=0, waves=0, w_lds=0, dz_scale=1.0):
         return None
     n = len(hs)
     return out[:n], (out[n] if len(w_ts) == n else None)
+
+
+def fwd_chain_wide(x, ws, bs, w_head, b_head, rows=0, waves=0):
+    """fwd_chain at hidden width H = 128 or 512 (GPU only,
+    csrc/fwd_chain_wide.hip); H is w_head's in_dims.
+
+    ws / bs: weights (H, in) and biases of the chain's layers, bottom
+    layer first; x: the input of the lowest one, (M, any multiple of 8):
+    the first layer always streams it.
+
+    Returns ([h_l, ...], probs), each bit-identical to linear_fwd(relu)
+    -> ... -> head_fwd_fused, or None, with nothing launched, outside
+    the kernel's contract: another H, C > 16, more than eight layers,
+    in_dims % 8 != 0, a tensor that is not bf16, contiguous, 16-byte
+    aligned and on the GPU, or an arm that is not built.  rows = waves =
+    0 is the shipped arm; CHAIN_WIDE_ARMS lists the others."""
+    if not _is_gpu(x):
+        return None
+    out = _ext_for(x).fwd_chain_wide(x, list(ws), list(bs), w_head, b_head,
+                                     int(rows), int(waves))
+    if not out:
+        return None
+    return out[:-1], out[-1]
+
+
+def bwd_chain_wide(probs, target, w_head_t, global_batch, hs, w_ts, rows=0,
+                   waves=0):
+    """bwd_chain at hidden width H = 128 or 512 (GPU only,
+    csrc/bwd_chain_wide.hip); H is w_head_t's row count.  hs / w_ts as
+    bwd_chain.  No dropout scale.
+
+    Returns (dz_head, [dz_l, ...], dx or None), each bit-identical to
+    head_bwd_fused -> relu_bwd -> linear_dgrad -> ..., or None, with
+    nothing launched, outside the kernel's contract (see
+    fwd_chain_wide)."""
+    if not _is_gpu(probs):
+        return None
+    out = _ext_for(probs).bwd_chain_wide(probs, target, w_head_t,
+                                         float(global_batch), list(hs),
+                                         list(w_ts), int(rows), int(waves))
+    if not out:
+        return None
+    n = len(hs)
+    return out[0], out[1:1 + n], (out[1 + n] if len(w_ts) == n else None)
 
 
 def xent_loss(probs, target, global_batch, eps=1e-9):
