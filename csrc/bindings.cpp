@@ -1163,6 +1163,69 @@ std::vector<torch::Tensor> fused_mlp_fwd(torch::Tensor x,
     return {amax, logits};
 }
 
+// The same for hidden widths that differ from layer to layer
+// (fused_mlp_taper.hip): the widths are read from the weights, each one of
+// 128 / 256 / 512 / 1024, equal ones included.  Raises, with nothing
+// allocated or launched, outside the kernel's contract.
+std::vector<torch::Tensor> fused_mlp_taper_fwd(torch::Tensor x,
+                                               std::vector<torch::Tensor> ws,
+                                               std::vector<torch::Tensor> bs,
+                                               bool want_logits, int64_t rows,
+                                               int64_t waves) {
+    check_bf16(x, "x");
+    const int64_t n = (int64_t)ws.size();
+    TORCH_CHECK(n >= 2 && n <= SS_FUSED_MLP_MAX + 1 && (int64_t)bs.size() == n,
+                "fused_mlp_taper_fwd takes 1..", SS_FUSED_MLP_MAX,
+                " hidden layers and a head, with one bias each");
+    TORCH_CHECK(x.dim() == 2 && x.size(0) >= 1 && x.size(1) >= 1 &&
+                    x.size(0) <= INT_MAX - 64 && x.size(1) <= INT_MAX / 2,
+                "x must be [M][in_dim], M and in_dim >= 1");
+    const int64_t M = x.size(0), K0 = x.size(1);
+    const void* wp[SS_FUSED_MLP_MAX + 1] = {};
+    const void* bp[SS_FUSED_MLP_MAX + 1] = {};
+    int widths[SS_FUSED_MLP_MAX] = {};
+    int64_t K = K0, wmin = 1024;
+    for (int64_t l = 0; l < n; ++l) {
+        check_bf16(ws[l], "w");
+        check_bf16(bs[l], "b");
+        TORCH_CHECK(ws[l].device() == x.device() &&
+                        bs[l].device() == x.device(),
+                    "x, weights and biases must share a device");
+        TORCH_CHECK(ws[l].dim() == 2 && ws[l].size(1) == K &&
+                        bs[l].numel() == ws[l].size(0),
+                    "layer ", l, ": shape does not continue the chain");
+        const int64_t N = ws[l].size(0);
+        if (l < n - 1) {
+            TORCH_CHECK(N == 128 || N == 256 || N == 512 || N == 1024,
+                        "hidden width must be 128, 256, 512 or 1024, is ", N);
+            widths[l] = (int)N;
+            wmin = std::min(wmin, N);
+        } else {
+            TORCH_CHECK(N >= 1 && N <= 16, "head width must be 1..16, is ", N);
+        }
+        TORCH_CHECK(aligned16(ws[l].data_ptr()), "layer ", l,
+                    ": weight must be 16-byte aligned");
+        wp[l] = ws[l].data_ptr();
+        bp[l] = bs[l].data_ptr();
+        K = N;
+    }
+    const int64_t C = K;
+    TORCH_CHECK(waves >= 0 && waves * 16 <= wmin, "fused_mlp_taper_fwd: ",
+                waves, " waves leave fewer than 16 columns of the ", wmin,
+                "-wide layer per wave");
+    auto amax = torch::empty({M}, x.options().dtype(torch::kInt32));
+    auto logits = torch::empty({want_logits ? M : 0, C},
+                               x.options().dtype(torch::kFloat));
+    TORCH_CHECK(ss_fused_mlp_taper(x.data_ptr(), wp, bp, widths, (int)(n - 1),
+                                   wp[n - 1], bp[n - 1], amax.data_ptr(),
+                                   want_logits ? logits.data_ptr() : nullptr,
+                                   (int)M, (int)K0, (int)C, (int)rows,
+                                   (int)waves, cur_stream()),
+                "fused_mlp_taper_fwd: no arm (rows, waves) = (", rows, ", ",
+                waves, ") for these widths");
+    return {amax, logits};
+}
+
 void transpose_bf16(torch::Tensor src, torch::Tensor dst) {
     check_bf16(src, "src");
     check_bf16(dst, "dst");
@@ -1306,6 +1369,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("fused_mlp_fwd", &fused_mlp_fwd,
           "fused serving forward, H in {128, 256, 512, 1024}, any batch -> "
           "(argmax, f32 logits or empty); raises outside the contract",
+          py::arg("x"), py::arg("ws"), py::arg("bs"),
+          py::arg("want_logits") = false, py::arg("rows") = 0,
+          py::arg("waves") = 0);
+    m.def("fused_mlp_taper_fwd", &fused_mlp_taper_fwd,
+          "fused serving forward, every hidden width its own one of {128, "
+          "256, 512, 1024}, any batch -> (argmax, f32 logits or empty); "
+          "raises outside the contract",
           py::arg("x"), py::arg("ws"), py::arg("bs"),
           py::arg("want_logits") = false, py::arg("rows") = 0,
           py::arg("waves") = 0);

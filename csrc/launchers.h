@@ -253,6 +253,21 @@ bool ss_fused_mlp_wide(const void* x, const void* const* w,
                        int in_dim, int H, int cout, int rows, int waves,
                        hipStream_t stream);
 
+// ---- fused_mlp_taper.hip
+// The same forward for hidden widths that differ from layer to layer:
+// x [M][in_dim] -> widths[0] (ReLU) -> .. -> widths[nhidden - 1] (ReLU) ->
+// cout, every width one of 128 / 256 / 512 / 1024 (equal ones included).
+// w[l] is [widths[l]][widths[l - 1]] ([widths[0]][in_dim] for l = 0),
+// w_head [cout][widths[nhidden - 1]]; everything else as above.  False,
+// with nothing launched, outside that contract or for a (rows, waves) that
+// is not built for the largest width or leaves a wave fewer than 16
+// columns of the narrowest layer.
+bool ss_fused_mlp_taper(const void* x, const void* const* w,
+                        const void* const* b, const int* widths, int nhidden,
+                        const void* w_head, const void* b_head, void* argmax,
+                        void* logits, int M, int in_dim, int cout, int rows,
+                        int waves, hipStream_t stream);
+
 // ---- elementwise.hip
 void ss_relu_fwd(const void* x, void* y, long n, hipStream_t stream);
 void ss_relu_bwd(const void* dy, const void* y, void* dx, long n,

@@ -90,7 +90,9 @@ def fused_forward_fn(model, batch, scores=False):
     (build_fused_plan); every other ReLU chain of one hidden width in
     {128, 256, 512, 1024} with a head of up to 16 classes, at any batch,
     and any request for scores, goes to csrc/fused_mlp_wide.hip through
-    F.fused_mlp_forward."""
+    F.fused_mlp_forward.  A ReLU chain whose hidden widths differ, each
+    one of those four (784,512,256,128,10), goes the same way to
+    csrc/fused_mlp_taper.hip."""
     from shallowspeed_amd.models import Linear
     from shallowspeed_amd.ops import functional as F
     from shallowspeed_amd.ops import load_ext

@@ -88,6 +88,7 @@ def build_ext(verbose=True):
         os.path.join(src_dir, "norm.hip"),
         os.path.join(src_dir, "fused_mlp.hip"),
         os.path.join(src_dir, "fused_mlp_wide.hip"),
+        os.path.join(src_dir, "fused_mlp_taper.hip"),
         os.path.join(src_dir, "fwd_chain_wide.hip"),
         os.path.join(src_dir, "bwd_chain_wide.hip"),
     ]

@@ -1168,11 +1168,20 @@ def row_argmax(x):
 FUSED_MLP_ARMS = {128: ((32, 4), (64, 4)), 256: ((32, 4), (64, 4), (64, 8)),
                   512: ((32, 8), (64, 8), (64, 16)),
                   1024: ((32, 8), (32, 16), (64, 8))}
+# largest width -> the (rows, waves) arms csrc/fused_mlp_taper.hip is built
+# for; a model takes those that leave a wave >= 16 columns of its narrowest
+# layer (min(widths) // waves >= 16)
+FUSED_MLP_TAPER_ARMS = {128: ((32, 4), (64, 4)),
+                        256: ((32, 4), (64, 4), (64, 8)),
+                        512: ((32, 8), (64, 8), (64, 16)),
+                        1024: ((32, 8), (32, 16), (64, 8))}
 _FUSED_DESC = OrderedDict()  # pointer tuple -> device table of the 256 kernel
 
 
 def fused_mlp_ok(x, ws, bs):
-    """The contract of csrc/fused_mlp_wide.hip, from the tensors alone."""
+    """The contract of csrc/fused_mlp_wide.hip (one hidden width) and
+    csrc/fused_mlp_taper.hip (a width per hidden layer), from the tensors
+    alone."""
     n = len(ws)
     if n < 2 or n > 9 or len(bs) != n:
         return False
@@ -1185,11 +1194,11 @@ def fused_mlp_ok(x, ws, bs):
         return False
     if any(w.dim() != 2 or w.data_ptr() % 16 for w in ws):
         return False
-    H, C = ws[0].shape[0], ws[-1].shape[0]
-    if H not in FUSED_MLP_ARMS or not 1 <= C <= 16:
+    dims = [x.shape[1]] + [w.shape[0] for w in ws]
+    if any(h not in FUSED_MLP_ARMS for h in dims[1:-1]) or not (
+            1 <= dims[-1] <= 16):
         return False
-    return all(tuple(w.shape) == (C if l == n - 1 else H,
-                                  x.shape[1] if l == 0 else H)
+    return all(tuple(w.shape) == (dims[l + 1], dims[l])
                and b.numel() == w.shape[0]
                for l, (w, b) in enumerate(zip(ws, bs)))
 
@@ -1198,8 +1207,9 @@ def fused_mlp_forward(x, ws, bs, logits=False, rows=0, waves=0):
     """The whole serving forward in one kernel (GPU only).
 
     ws / bs: weights and biases of the Linear layers, bottom first: 1..8
-    hidden layers (H, in) with ReLU, H in {128, 256, 512, 1024}, then the
-    head (cout <= 16, H).  x: (M, in_dim) bf16, any M >= 1, any in_dim.
+    hidden layers (N_l, N_{l-1}) with ReLU, every N_l in {128, 256, 512,
+    1024}, then the head (cout <= 16, N).  x: (M, in_dim) bf16, any
+    M >= 1, any in_dim.
 
       h_l = bf16(relu(h_{l-1} @ W_l^T + b_l)) ; z = h @ W_head^T + b_head
 
@@ -1209,14 +1219,27 @@ def fused_mlp_forward(x, ws, bs, logits=False, rows=0, waves=0):
     for CPU tensors or shapes outside the contract (the caller takes the
     per-layer path).
 
-    H = 256 with M % 64 == 0 and no logits runs csrc/fused_mlp.hip, as
-    before; everything else csrc/fused_mlp_wide.hip, where rows / waves
-    select a measured arm (0: the shipped choice)."""
+    With one hidden width H: H = 256 with M % 64 == 0 and no logits runs
+    csrc/fused_mlp.hip, as before; everything else csrc/fused_mlp_wide.hip,
+    where rows / waves select a measured arm (0: the shipped choice).
+    Hidden widths that differ run csrc/fused_mlp_taper.hip; there a
+    (rows, waves) that FUSED_MLP_TAPER_ARMS does not list for the largest
+    width, or that leaves a wave fewer than 16 columns of the narrowest
+    layer, also returns None."""
     ws, bs = list(ws), list(bs)
     if not fused_mlp_ok(x, ws, bs):
         return None
     ext = _ext_for(x)
     M, H = x.shape[0], ws[0].shape[0]
+    widths = [w.shape[0] for w in ws[:-1]]
+    if any(h != H for h in widths):
+        if (rows or waves) and (
+                (rows, waves) not in FUSED_MLP_TAPER_ARMS[max(widths)]
+                or min(widths) // waves < 16):
+            return None
+        amax, z = ext.fused_mlp_taper_fwd(x, ws, bs, bool(logits), int(rows),
+                                          int(waves))
+        return (amax, z) if logits else amax
     if H == 256 and M % 64 == 0 and not logits and not rows and not waves:
         ptrs = tuple(p for w, b in zip(ws, bs)
                      for p in (w.data_ptr(), b.data_ptr()))
