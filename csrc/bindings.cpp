@@ -795,14 +795,23 @@ std::vector<torch::Tensor> bwd_chain_stage(torch::Tensor dout,
 // is left untouched when the launch is refused.
 // head == false is the stage arm (fwd_chain_stage below): no w_head /
 // b_head / zero, and no probs in the result.
+// drop != null: the arms under dropout (fwd_chain_dropout below), refused
+// as well when no layer of the launch draws a mask or the last row is no
+// 32-bit sample id.
 static std::vector<torch::Tensor> fwd_chain_any(
     bool head, const torch::Tensor& x, const std::vector<torch::Tensor>& ws,
     const std::vector<torch::Tensor>& bs, const torch::Tensor& w_head,
     const torch::Tensor& b_head, int64_t rows, int64_t waves, int64_t l1,
-    int64_t kloop, const std::optional<torch::Tensor>& zero) {
+    int64_t kloop, const std::optional<torch::Tensor>& zero,
+    const FwdChainDrop* drop = nullptr) {
     constexpr int64_t H = 256;
     const int64_t n = (int64_t)ws.size();
     if (n < 1 || n > SS_FWD_CHAIN_MAX || (int64_t)bs.size() != n) return {};
+    if (drop && (drop->on == 0 || (drop->on >> n) != 0 || x.dim() != 2 ||
+                 (int64_t)drop->row_first +
+                         (x.size(0) - 1) * (int64_t)drop->row_stride >
+                     (int64_t)UINT_MAX))
+        return {};
     if (kloop < 0 || kloop > 2) return {};
     void* zero_p = nullptr;
     int64_t zero_bytes = 0;
@@ -840,17 +849,30 @@ static std::vector<torch::Tensor> fwd_chain_any(
         hp[l] = out.back().data_ptr();
     }
     if (!head) {
-        if (!ss_fwd_chain_stage(x.data_ptr(), wp, bp, hp, (int)n, (int)M,
-                                (int)K0, (int)H, (int)rows, (int)waves,
-                                (int)l1, (int)kloop, cur_stream()))
+        if (!(drop ? ss_fwd_chain_stage_drop(
+                         x.data_ptr(), wp, bp, hp, (int)n, (int)M, (int)K0,
+                         (int)H, (int)rows, (int)waves, (int)l1, (int)kloop,
+                         *drop, cur_stream())
+                   : ss_fwd_chain_stage(x.data_ptr(), wp, bp, hp, (int)n,
+                                        (int)M, (int)K0, (int)H, (int)rows,
+                                        (int)waves, (int)l1, (int)kloop,
+                                        cur_stream())))
             return {};
         return out;
     }
     out.push_back(torch::empty({M, C}, x.options()));
-    if (!ss_fwd_chain(x.data_ptr(), wp, bp, hp, (int)n, w_head.data_ptr(),
-                      b_head.data_ptr(), out.back().data_ptr(), (int)M,
-                      (int)K0, (int)H, (int)C, (int)rows, (int)waves, (int)l1,
-                      (int)kloop, zero_p, (long)zero_bytes, cur_stream()))
+    if (!(drop ? ss_fwd_chain_drop(
+                     x.data_ptr(), wp, bp, hp, (int)n, w_head.data_ptr(),
+                     b_head.data_ptr(), out.back().data_ptr(), (int)M,
+                     (int)K0, (int)H, (int)C, (int)rows, (int)waves, (int)l1,
+                     (int)kloop, zero_p, (long)zero_bytes, *drop,
+                     cur_stream())
+               : ss_fwd_chain(x.data_ptr(), wp, bp, hp, (int)n,
+                              w_head.data_ptr(), b_head.data_ptr(),
+                              out.back().data_ptr(), (int)M, (int)K0, (int)H,
+                              (int)C, (int)rows, (int)waves, (int)l1,
+                              (int)kloop, zero_p, (long)zero_bytes,
+                              cur_stream())))
         return {};
     return out;
 }
@@ -877,6 +899,76 @@ std::vector<torch::Tensor> fwd_chain_stage(torch::Tensor x,
                                            int64_t l1, int64_t kloop) {
     return fwd_chain_any(false, x, ws, bs, x, x, rows, waves, l1, kloop,
                          std::nullopt);
+}
+
+// The dropout block of the two bindings below from what Python passes
+// (ops/functional.py computes thr and scale per layer, the one
+// definition; drops[l] = layer l has p > 0).  False when a list has not
+// one entry per layer or a field does not fit its 32 bits.
+static bool fwd_chain_drop_block(FwdChainDrop& d, int64_t n, int64_t key0,
+                                 int64_t key1, int64_t step,
+                                 const std::vector<int64_t>& layers,
+                                 const std::vector<int64_t>& thrs,
+                                 const std::vector<double>& scales,
+                                 const std::vector<bool>& drops,
+                                 int64_t row_first, int64_t row_stride) {
+    auto u32 = [](int64_t v) { return v >= 0 && v <= (int64_t)UINT_MAX; };
+    if (n < 1 || n > SS_FWD_CHAIN_MAX || (int64_t)layers.size() != n ||
+        (int64_t)thrs.size() != n || (int64_t)scales.size() != n ||
+        (int64_t)drops.size() != n || !u32(key0) || !u32(key1) ||
+        !u32(step) || !u32(row_first) || !u32(row_stride))
+        return false;
+    d = {};
+    d.key0 = (unsigned)key0;
+    d.key1 = (unsigned)key1;
+    d.step = (unsigned)step;
+    d.row_first = (unsigned)row_first;
+    d.row_stride = (unsigned)row_stride;
+    for (int64_t l = 0; l < n; ++l) {
+        if (!u32(layers[l]) || !u32(thrs[l])) return false;
+        d.layer[l] = (unsigned)layers[l];
+        d.thr[l] = (unsigned)thrs[l];
+        d.scale[l] = (float)scales[l];
+        d.on |= (unsigned)drops[l] << l;
+    }
+    return true;
+}
+
+// Forward chain under dropout (fwd_chain_drop.hip): fwd_chain with the
+// mask of layer l (counter word layers[l], thrs[l], scales[l]) in its
+// epilogue; a layer with drops[l] false runs the plain epilogue.  Same
+// result list, EMPTY with nothing allocated, launched or zeroed outside
+// the contract.
+std::vector<torch::Tensor> fwd_chain_dropout(
+    torch::Tensor x, std::vector<torch::Tensor> ws,
+    std::vector<torch::Tensor> bs, torch::Tensor w_head, torch::Tensor b_head,
+    int64_t key0, int64_t key1, int64_t step, std::vector<int64_t> layers,
+    std::vector<int64_t> thrs, std::vector<double> scales,
+    std::vector<bool> drops, int64_t row_first, int64_t row_stride,
+    int64_t rows, int64_t waves, int64_t l1, int64_t kloop,
+    std::optional<torch::Tensor> zero) {
+    FwdChainDrop d;
+    if (!fwd_chain_drop_block(d, (int64_t)ws.size(), key0, key1, step, layers,
+                              thrs, scales, drops, row_first, row_stride))
+        return {};
+    return fwd_chain_any(true, x, ws, bs, w_head, b_head, rows, waves, l1,
+                         kloop, zero, &d);
+}
+
+// Its stage arm (fwd_chain_stage_drop.hip): [h_0, ..., h_{n-1}] or EMPTY.
+std::vector<torch::Tensor> fwd_chain_stage_dropout(
+    torch::Tensor x, std::vector<torch::Tensor> ws,
+    std::vector<torch::Tensor> bs, int64_t key0, int64_t key1, int64_t step,
+    std::vector<int64_t> layers, std::vector<int64_t> thrs,
+    std::vector<double> scales, std::vector<bool> drops, int64_t row_first,
+    int64_t row_stride, int64_t rows, int64_t waves, int64_t l1,
+    int64_t kloop) {
+    FwdChainDrop d;
+    if (!fwd_chain_drop_block(d, (int64_t)ws.size(), key0, key1, step, layers,
+                              thrs, scales, drops, row_first, row_stride))
+        return {};
+    return fwd_chain_any(false, x, ws, bs, x, x, rows, waves, l1, kloop,
+                         std::nullopt, &d);
 }
 
 // Wide forward chain (fwd_chain_wide.hip): fwd_chain at H = 128 or 512,
@@ -1337,6 +1429,24 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "256-wide ReLU layers of a headless pipeline stage in one launch "
           "-> [h_l...], or [] outside the contract",
           py::arg("x"), py::arg("ws"), py::arg("bs"), py::arg("rows") = 0,
+          py::arg("waves") = 0, py::arg("l1") = 0, py::arg("kloop") = 0);
+    m.def("fwd_chain_dropout", &fwd_chain_dropout,
+          "fwd_chain with each layer's dropout mask in its epilogue -> "
+          "[h_l..., probs], or [] outside the contract",
+          py::arg("x"), py::arg("ws"), py::arg("bs"), py::arg("w_head"),
+          py::arg("b_head"), py::arg("key0"), py::arg("key1"),
+          py::arg("step"), py::arg("layers"), py::arg("thrs"),
+          py::arg("scales"), py::arg("drops"), py::arg("row_first"),
+          py::arg("row_stride"), py::arg("rows") = 0, py::arg("waves") = 0,
+          py::arg("l1") = 0, py::arg("kloop") = 0,
+          py::arg("zero") = py::none());
+    m.def("fwd_chain_stage_dropout", &fwd_chain_stage_dropout,
+          "fwd_chain_stage with each layer's dropout mask in its epilogue "
+          "-> [h_l...], or [] outside the contract",
+          py::arg("x"), py::arg("ws"), py::arg("bs"), py::arg("key0"),
+          py::arg("key1"), py::arg("step"), py::arg("layers"),
+          py::arg("thrs"), py::arg("scales"), py::arg("drops"),
+          py::arg("row_first"), py::arg("row_stride"), py::arg("rows") = 0,
           py::arg("waves") = 0, py::arg("l1") = 0, py::arg("kloop") = 0);
     m.def("bwd_chain_stage", &bwd_chain_stage,
           "256-wide ReLU dgrads of a headless pipeline stage from dout in "

@@ -66,3 +66,26 @@ __host__ __device__ __forceinline__ unsigned dropout_sample(
     const DropoutArgs& d, unsigned row) {
     return d.row_first + row * d.row_stride;
 }
+
+// Keep bits of one 16x16 MFMA C fragment with ONE Philox call per lane
+// (gemm_nt_kernel's epilogue form).  In that layout the four lanes of a
+// quad (lane & ~3 .. +3) hold four consecutive columns, lane & 3 ==
+// col & 3, and each lane holds rows r = 0..3 of its column.  Lane q of
+// the quad passes the sample of row q and the quad's column group; the
+// quad then exchanges the bits by DPP quad_perm broadcasts.  Bit r of
+// the result: row r of this lane's column is kept.  Every lane of the
+// quad must make the call.
+__device__ __forceinline__ unsigned dropout_keep4_frag(
+    const DropoutArgs& d, unsigned sample_q, unsigned cgroup, int q) {
+    const unsigned mine = dropout_keep4(d, sample_q, cgroup);
+    const unsigned b0 =
+        __builtin_amdgcn_update_dpp(0, (int)mine, 0x00, 0xf, 0xf, true);
+    const unsigned b1 =
+        __builtin_amdgcn_update_dpp(0, (int)mine, 0x55, 0xf, 0xf, true);
+    const unsigned b2 =
+        __builtin_amdgcn_update_dpp(0, (int)mine, 0xaa, 0xf, 0xf, true);
+    const unsigned b3 =
+        __builtin_amdgcn_update_dpp(0, (int)mine, 0xff, 0xf, 0xf, true);
+    return ((b0 >> q) & 1) | (((b1 >> q) & 1) << 1) | (((b2 >> q) & 1) << 2) |
+           (((b3 >> q) & 1) << 3);
+}

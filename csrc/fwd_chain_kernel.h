@@ -8,6 +8,14 @@
 //                        h_top on: no W_head / b_head / probs and no
 //                        zeroing, and the kernel ends after the top
 //                        layer's h store
+//   FWD_CHAIN_DROP    (optional, default 0) the arms under dropout
+//                     (fwd_chain_drop.hip, fwd_chain_stage_drop.hip): a
+//                     FwdChainDrop block follows the layers, and a layer
+//                     whose bit is set in it masks its epilogue.
+//                     2: the keep bits are drawn before the layer's K
+//                        loop (shipped)
+//                     1: in the epilogue (the measured alternative,
+//                        profiles/r22_fwd_chain_dropout.md)
 //
 // The arms share text through the preprocessor and not through a
 // function template for chain_dev.h's reason: with the body as a
@@ -19,6 +27,13 @@
 
 #include "chain_dev.h"
 #include "launchers.h"
+
+#ifndef FWD_CHAIN_DROP
+#define FWD_CHAIN_DROP 0
+#endif
+#if FWD_CHAIN_DROP
+#include "dropout_dev.h"
+#endif
 
 // The layers of one launch, bottom first.  Passed BY VALUE: nothing to
 // upload, nothing to keep alive, and legal under graph capture.
@@ -37,6 +52,9 @@ __global__ __launch_bounds__(NW * 64, NW / 2)
 void FWD_CHAIN_KERNEL(
     const __bf16* __restrict__ x,       // [M][K0]: input of layer 0
     const FwdChainLayers L, int nlayers,
+#if FWD_CHAIN_DROP
+    const FwdChainDrop D,
+#endif
 #if FWD_CHAIN_HEAD
     const __bf16* __restrict__ W_head,  // [C][256]
     const __bf16* __restrict__ b_head,  // [C]
@@ -91,11 +109,57 @@ void FWD_CHAIN_KERNEL(
 #pragma unroll
             for (int j = 0; j < FN; ++j) acc[i][j] = {0.f, 0.f, 0.f, 0.f};
     };
+#if FWD_CHAIN_DROP
+    // Keep bits of a layer: fragment (i, j) owns nibble i * FN + j, bit r
+    // of it is row r of this lane's column (dropout_keep4_frag), so a
+    // layer's mask lives in one register (two at 64 rows on four waves).
+    // One Philox call per fragment and lane: lane & 3 draws tile row
+    // i * 16 + kch * 4 + (lane & 3) for the quad's column group.  Rows
+    // past M draw as well (the quad exchange needs every lane) and are
+    // never stored.
+    constexpr int NKB = (FM * FN + 7) / 8;
+    unsigned kb[NKB];
+    auto draw_mask = [&](int l) {
+        const DropoutArgs d = {D.key0,      D.key1,       D.layer[l], D.step,
+                               D.row_first, D.row_stride, D.thr[l],   1.f};
+        const int q = lane & 3;
+#pragma unroll
+        for (int n = 0; n < NKB; ++n) kb[n] = 0u;
+#pragma unroll
+        for (int i = 0; i < FM; ++i)
+#pragma unroll
+            for (int j = 0; j < FN; ++j)
+                kb[(i * FN + j) / 8] |=
+                    dropout_keep4_frag(
+                        d, dropout_sample(d, row0 + i * 16 + kch * 4 + q),
+                        (unsigned)(wave * WN + j * 16 + lrow) >> 2, q)
+                    << ((i * FN + j) % 8 * 4);
+    };
+    // block-uniform: whether layer l draws a mask at all
+    auto drops = [&](int l) { return (D.on >> l) & 1u; };
+#endif
     // acc -> tile through the gemm_nt_kernel epilogue (bias, ReLU, one
-    // rounding), then the tile -> h_l as 16-B row-contiguous stores.
-    // The caller has made sure that no wave still reads the tile.
+    // rounding; under dropout the mask and the scale ahead of the
+    // rounding, as gemm_nt_kernel<.., DROPOUT>), then the tile -> h_l as
+    // 16-B row-contiguous stores.  The caller has made sure that no wave
+    // still reads the tile.
     auto finish_layer = [&](int l, const float (&bv)[FN]) {
-        CHAIN_ACC_TO_TILE(acc, tile, v += bv[j]; v = v > 0.f ? v : 0.f)
+#if FWD_CHAIN_DROP
+        if (drops(l)) {
+#if FWD_CHAIN_DROP == 1
+            draw_mask(l);
+#endif
+            const float scale = D.scale[l];
+            CHAIN_ACC_TO_TILE(
+                acc, tile, v += bv[j]; v = v > 0.f ? v : 0.f;
+                v = (kb[(i * FN + j) / 8] >> ((i * FN + j) % 8 * 4 + r)) & 1u
+                        ? v * scale
+                        : 0.f)
+        } else
+#endif
+        {
+            CHAIN_ACC_TO_TILE(acc, tile, v += bv[j]; v = v > 0.f ? v : 0.f)
+        }
         __syncthreads();
         gbf16* const ho = (gbf16*)L.h[l];
         CHAIN_FOR_PIECES(i, r, col) {
@@ -120,6 +184,9 @@ void FWD_CHAIN_KERNEL(
         const gbf16* const w = (const gbf16*)L.w[0];
         float bv[FN];
         load_bias(0, bv);
+#if FWD_CHAIN_DROP == 2
+        if (drops(0)) draw_mask(0);
+#endif
         const int nsteps = cdiv(K0, 32);
         const int nchunks = cdiv(K0, KC);
         bf16x8 xr[XP];
@@ -266,6 +333,9 @@ void FWD_CHAIN_KERNEL(
         const gbf16* const w = (const gbf16*)L.w[l];
         float bv[FN];
         load_bias(l, bv);
+#if FWD_CHAIN_DROP == 2
+        if (drops(l)) draw_mask(l);
+#endif
         zero_acc();
         if constexpr (AH) {
             CHAIN_LAYER_MMA_AHEAD(acc, tile, w)
@@ -325,13 +395,18 @@ void FWD_CHAIN_KERNEL(
 // zero_ptr / zero_bytes: see launchers.h; the launch is refused when
 // they are not 4-B granular.
 // This arm's launch (the stage arm's callers pass null head pointers,
-// C = 1 and no zeroing).
+// C = 1 and no zeroing).  The arms under dropout take their FwdChainDrop
+// block and refuse one that masks no layer of the launch or whose last
+// row is no 32-bit sample id.
 static bool fwd_chain_launch(const void* x, const void* const* w,
                              const void* const* b, void* const* h,
                              int nlayers, const void* W_head,
                              const void* b_head, void* probs, int M, int K0,
                              int H, int C, int rows, int waves, int l1,
                              int kloop, void* zero_ptr, long zero_bytes,
+#if FWD_CHAIN_DROP
+                             const FwdChainDrop& D,
+#endif
                              hipStream_t st) {
     if (M < 1 || M > INT32_MAX - 64 || H != 256 || C < 1 || C > 16 ||
         nlayers < 1 || nlayers > SS_FWD_CHAIN_MAX || K0 < 8 || K0 % 8 != 0)
@@ -340,6 +415,12 @@ static bool fwd_chain_launch(const void* x, const void* const* w,
         (zero_bytes > 0 && (!zero_ptr || ((uintptr_t)zero_ptr & 3))))
         return false;
     if (!aligned16(x)) return false;
+#if FWD_CHAIN_DROP
+    if (D.on == 0 || (D.on >> nlayers) != 0 ||
+        (unsigned long)D.row_first +
+                (unsigned long)(M - 1) * D.row_stride > UINT32_MAX)
+        return false;
+#endif
 #if FWD_CHAIN_HEAD
     if (!aligned16(W_head) || !aligned16(b_head) || !aligned16(probs))
         return false;
@@ -377,6 +458,9 @@ static bool fwd_chain_launch(const void* x, const void* const* w,
                     (FWD_CHAIN_KERNEL<R, NW, streamed.value, AH>),
                     dim3(cdiv(M, R)), dim3(NW * 64), 0, st, (const __bf16*)x,
                     L, nlayers,
+#if FWD_CHAIN_DROP
+                    D,
+#endif
 #if FWD_CHAIN_HEAD
                     (const __bf16*)W_head, (const __bf16*)b_head,
                     (__bf16*)probs, M, K0, C, (unsigned*)zero_ptr,

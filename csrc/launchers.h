@@ -210,6 +210,35 @@ bool ss_fwd_chain_stage(const void* x, const void* const* w,
                         int M, int K0, int H, int rows, int waves, int l1,
                         int kloop, hipStream_t stream);
 
+// ---- fwd_chain_drop.hip / fwd_chain_stage_drop.hip
+// The two launches above under dropout: layer l's epilogue is
+// gemm_nt_kernel<.., DROPOUT>'s, v = keep ? relu(acc + b) * scale : +0
+// with one rounding, and the dropped-out tile is the next layer's input.
+// Passed by value.  Row i of the launch is sample row_first + i *
+// row_stride; layer l draws with counter word layer[l].  Bit l of `on`
+// clear (p = 0): that layer runs the plain epilogue and draws nothing.
+struct FwdChainDrop {
+    unsigned key0, key1, step;  // seed low / high word, counter word 3
+    unsigned row_first, row_stride;
+    unsigned on;
+    unsigned layer[SS_FWD_CHAIN_MAX];
+    unsigned thr[SS_FWD_CHAIN_MAX];  // keep when word < thr
+    float scale[SS_FWD_CHAIN_MAX];   // float32(1 / (1 - p))
+};
+// ss_fwd_chain's contract, plus: `on` names at least one layer and none
+// at or past nlayers, and the last row's sample id stays below 2^32.
+bool ss_fwd_chain_drop(const void* x, const void* const* w,
+                       const void* const* b, void* const* h, int nlayers,
+                       const void* W_head, const void* b_head, void* probs,
+                       int M, int K0, int H, int C, int rows, int waves,
+                       int l1, int kloop, void* zero_ptr, long zero_bytes,
+                       const FwdChainDrop& drop, hipStream_t stream);
+bool ss_fwd_chain_stage_drop(const void* x, const void* const* w,
+                             const void* const* b, void* const* h,
+                             int nlayers, int M, int K0, int H, int rows,
+                             int waves, int l1, int kloop,
+                             const FwdChainDrop& drop, hipStream_t stream);
+
 // ---- fwd_chain_wide.hip / bwd_chain_wide.hip
 // The headed chains at H = 128 and 512, with ss_fwd_chain's and
 // ss_bwd_chain's pointer lists.  The first layer always streams x (any

@@ -17,7 +17,20 @@ another, not with profiler kernel times.
               side (kloop 1 = B one step ahead, 2 = three steps ahead),
               at M = 16384, 32768 (two rounds of 64-row tiles) and 4096
               (32 rows), with and without the gradient buffer's zeros
-              riding in the launch (against the memset launch)"""
+              riding in the launch (against the memset launch)
+
+With the argument `dropout` it runs this section alone:
+
+  dropout     the flagship forward under dropout (p = 0.2 on the three
+              ReLU layers) at M = 16384 and 4096: 3 x gemm_nt_dropout +
+              head_fwd_fused (what the model launches with the switch
+              off), the one fwd_chain_dropout launch in its shipped arm,
+              and the plain fwd_chain at the same shape, which prices the
+              mask, and then the model's training step with the switch
+              off and on.  The keep bits are drawn ahead of each K loop;
+              the build with them drawn in the epilogue is
+              FWD_CHAIN_DROP 1 in csrc/fwd_chain_drop.hip
+              (profiles/r22_fwd_chain_dropout.md)"""
 import statistics
 import sys
 
@@ -89,6 +102,59 @@ def gemm_then_chain():
     h = e.gemm_nt(x, w1, b1, empty, True)
     return F.fwd_chain(h, ws, bs, w_head, b_head, 64, 8, l1=1)
 
+
+def dropout_section():
+    p, seed, layers = 0.2, 0x1234567887654321, (0, 1, 2)
+    thr, scale = F.dropout_params(p)
+    k0, k1 = seed & 0xFFFFFFFF, seed >> 32
+    wl, bl = [w1] + ws, [b1] + bs
+
+    def per_layer(xm):
+        h = xm
+        for l, w, b in zip(layers, wl, bl):
+            h = e.gemm_nt_dropout(h, w, b, k0, k1, 7, l, 0, 1, thr, scale,
+                                  True)
+        return e.head_fwd_fused(h, w_head, b_head)
+
+    for m in (16384, 4096):
+        xm = rnd(m, IN0)
+        print(f"forward under dropout p={p}, M={m} in={IN0} H={H} C={C}")
+        bench({
+            "3 x gemm_nt_dropout + head_fwd_fused": lambda: per_layer(xm),
+            "fwd_chain_dropout": lambda: F.fwd_chain_dropout(
+                xm, wl, bl, w_head, b_head, seed, 7, layers, (p,) * 3, 0, 1),
+            "fwd_chain (no mask)": lambda: F.fwd_chain(
+                xm, wl, bl, w_head, b_head),
+        })
+
+    # the training step (zero_grad, forward, backward, SGD) of the
+    # flagship model, the switch off against on, on one model
+    from shallowspeed_amd.models import MLP, SGD
+
+    for m in (16384, 4096):
+        model = MLP([IN0, H, H, H, C], 0, 1, m, dropout=p,
+                    dropout_seed=seed).materialize_device(dev)
+        opt = SGD(model.parameters(), lr=0.01)
+        xm = rnd(m, IN0)
+        t = torch.eye(C)[torch.arange(m) % C].to(dev).bfloat16()
+
+        def step(on):
+            F.set_fwd_chain_dropout(on)
+            model.zero_grad()
+            model.forward(xm, 0)
+            model.backward(t, 0)
+            opt.step()
+            model.dropout_step += 1
+
+        print(f"training step under dropout p={p}, M={m}")
+        bench({"step, SS_FWD_CHAIN_DROPOUT off": lambda: step(False),
+               "step, SS_FWD_CHAIN_DROPOUT on": lambda: step(True)})
+    F.set_fwd_chain_dropout(False)
+
+
+if sys.argv[1:] == ["dropout"]:
+    dropout_section()
+    sys.exit(0)
 
 print(f"forward from h1, M={M} H={H} C={C}")
 arms = {"2 x gemm_nt + head_fwd_fused": replaced_from_h1}

@@ -688,6 +688,36 @@ class Sequential(Module):
             return None
         return self._fwd_chain_plan(top=len(self.layers) - 1)
 
+    def _fwd_drop_plan(self):
+        """_fwd_chain_plan (with a head pair) or _fwd_stage_plan
+        (without) by the same rules minus the dropout refusal: the layers
+        that F.fwd_chain_dropout / F.fwd_chain_stage_dropout take in
+        training mode, and F.fwd_chain / F.fwd_chain_stage in eval mode,
+        where a dropout layer's forward is the plain one.  Still None
+        with an fp8 forward on a layer it would take.  Opt-in
+        (F.fwd_chain_dropout_enabled()) and consulted only where those
+        plans are None."""
+        if not F.fwd_chain_dropout_enabled() or not F.fwd_chain_enabled():
+            return None
+        top = None
+        if self._head_pair() is None:
+            top = len(self.layers) - 1
+        elif not F.head_fused() or self._chain_head_pair() is None:
+            return None
+        plan = []
+        for i in self._chain_run(top):
+            layer = self.layers[i]
+            streamed = layer.in_dims != self._CHAIN_WIDTH
+            if streamed and not (F.fwd_chain_l1() and layer.in_dims >= 8
+                                 and layer.in_dims % 8 == 0):
+                break
+            if layer.fp8_fwd:
+                return None
+            plan.append(i)
+            if streamed:
+                break
+        return plan[::-1] or None
+
     def _wide_head_width(self, rows=None):
         """in_dims of the head pair's Linear when the wide chain kernels
         (F.fwd_chain_wide / F.bwd_chain_wide) run under it at `rows`
@@ -751,7 +781,8 @@ class Sequential(Module):
                 break
         return plan or None
 
-    def _forward_chain(self, plan, lin, head, x, mubatch_id, launch=None):
+    def _forward_chain(self, plan, lin, head, x, mubatch_id, launch=None,
+                       drop=False):
         """Forward of the planned ReLU layers and the head pair through
         ONE F.fwd_chain launch, leaving the stashes the layers' own
         forwards leave.  Returns probs, or None with no stash touched
@@ -759,11 +790,26 @@ class Sequential(Module):
         = None (a stage plan): ONE F.fwd_chain_stage launch, which never
         takes a deferred zero_grad along; returns the top layer's
         output.  launch (a wide plan): F.fwd_chain_wide in place of
-        F.fwd_chain, which takes no deferred zero_grad along either."""
+        F.fwd_chain, which takes no deferred zero_grad along either.
+        drop (a _fwd_drop_plan): where a planned layer drops out in this
+        forward (training mode), F.fwd_chain_dropout /
+        F.fwd_chain_stage_dropout with the layers' own mask keys, so the
+        stashed y are the post-dropout outputs Linear._forward_dropout
+        leaves; else the plain launch."""
         chain = [self.layers[i] for i in plan]
+        dargs = None
+        if drop and any(l._drop_on() for l in chain):
+            # one DropoutState for the whole Sequential: every layer's key
+            # differs in its layer index and p alone
+            seed, step, _, first, stride, _ = chain[0]._drop_key(mubatch_id)
+            dargs = (seed, step, [l.layer_index for l in chain],
+                     [l.dropout if l._drop_on() else 0.0 for l in chain],
+                     first, stride)
         if lin is None:
-            hs = F.fwd_chain_stage(x, [l.weight.compute() for l in chain],
-                                   [l.bias.compute() for l in chain])
+            ws = [l.weight.compute() for l in chain]
+            bs = [l.bias.compute() for l in chain]
+            hs = F.fwd_chain_stage_dropout(x, ws, bs, *dargs) if dargs \
+                else F.fwd_chain_stage(x, ws, bs)
             if hs is None:
                 return None
             for layer, h in zip(chain, hs):
@@ -780,7 +826,12 @@ class Sequential(Module):
         args = (x, [l.weight.compute() for l in chain],
                 [l.bias.compute() for l in chain],
                 lin.weight.compute(), lin.bias.compute())
-        res = launch(*args) if launch else F.fwd_chain(*args, zero=zero)
+        if launch:
+            res = launch(*args)
+        elif dargs:
+            res = F.fwd_chain_dropout(*args, *dargs, zero=zero)
+        else:
+            res = F.fwd_chain(*args, zero=zero)
         if res is None:
             return None
         if zero is not None:
@@ -800,21 +851,25 @@ class Sequential(Module):
         n_plain = len(self.layers) - 2 if pair else len(self.layers)
         plan = None
         wide = None
+        drop = False
         if inputs.is_cuda:
             plan = self._fwd_chain_plan() if pair else self._fwd_stage_plan()
             if plan is None and pair:
                 plan = self._fwd_wide_plan(inputs.shape[0])
                 wide = F.fwd_chain_wide if plan else None
+            if plan is None:
+                plan = self._fwd_drop_plan()
+                drop = plan is not None
         if plan:
-            if not pair or wide:
+            if not pair or wide or drop:
                 # the stage and the wide launch take no deferred
-                # zero_grad along
+                # zero_grad along, and none is deferred under dropout
                 self._settle_zero_grad()
             # layers below the chain run their own forward first
             for layer in self.layers[:plan[0]]:
                 x = layer.forward(x, mubatch_id)
             s = self._forward_chain(plan, *(pair or (None, None)), x,
-                                    mubatch_id, wide)
+                                    mubatch_id, wide, drop)
             if s is not None:
                 return s
             first = plan[0]

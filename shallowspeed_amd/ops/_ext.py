@@ -85,6 +85,8 @@ def build_ext(verbose=True):
         os.path.join(src_dir, "fwd_chain.hip"),
         os.path.join(src_dir, "bwd_chain_stage.hip"),
         os.path.join(src_dir, "fwd_chain_stage.hip"),
+        os.path.join(src_dir, "fwd_chain_drop.hip"),
+        os.path.join(src_dir, "fwd_chain_stage_drop.hip"),
         os.path.join(src_dir, "norm.hip"),
         os.path.join(src_dir, "fused_mlp.hip"),
         os.path.join(src_dir, "fused_mlp_wide.hip"),

@@ -194,6 +194,31 @@ def fwd_chain_enabled() -> bool:
     return _FWD_CHAIN
 
 
+_FWD_CHAIN_DROPOUT = None
+
+
+def set_fwd_chain_dropout(flag: bool):
+    """Let a model with dropout on its 256-wide ReLU layers run its
+    forward as one chain kernel too (Sequential._fwd_drop_plan): in
+    training mode fwd_chain_dropout / fwd_chain_stage_dropout, the mask
+    in each layer's epilogue; in eval mode, where the forward is the
+    plain one, fwd_chain / fwd_chain_stage.  Every h_l and probs keeps
+    its bits.  Default OFF; SS_FWD_CHAIN_DROPOUT=1 (read once) turns it
+    on (profiles/r22_fwd_chain_dropout.md)."""
+    global _FWD_CHAIN_DROPOUT
+    _FWD_CHAIN_DROPOUT = bool(flag)
+
+
+def fwd_chain_dropout_enabled() -> bool:
+    global _FWD_CHAIN_DROPOUT
+    if _FWD_CHAIN_DROPOUT is None:
+        import os
+
+        _FWD_CHAIN_DROPOUT = \
+            os.environ.get("SS_FWD_CHAIN_DROPOUT", "0") == "1"
+    return _FWD_CHAIN_DROPOUT
+
+
 _CHAIN_WIDE = None
 CHAIN_WIDE_WIDTHS = (128, 512)
 # (rows, waves) arms the wide chain kernels are built with, per width
@@ -836,6 +861,75 @@ def fwd_chain_stage(x, ws, bs, rows=0, waves=0, l1=0, kloop=0):
         return None
     out = _ext_for(x).fwd_chain_stage(x, list(ws), list(bs), int(rows),
                                       int(waves), int(l1), int(kloop))
+    return out or None
+
+
+def _chain_drop_args(x, seed, step, layers, ps, row_first, row_stride):
+    """The dropout arguments of the two ops below as the extension takes
+    them, or None when they cannot describe a launch (the op then refuses
+    as the kernel's contract does)."""
+    layers, ps = [int(i) for i in layers], [float(p) for p in ps]
+    step, row_first, row_stride = int(step), int(row_first), int(row_stride)
+    if len(layers) != len(ps) or min(
+            [step, row_first, row_stride] + layers) < 0 \
+            or max([step, row_first, row_stride] + layers) > _U32 \
+            or x.dim() != 2 \
+            or row_first + max(x.shape[0] - 1, 0) * row_stride > _U32:
+        return None
+    params = [dropout_params(p) for p in ps]
+    return (*_seed_words(seed), step, layers, [t for t, _ in params],
+            [s for _, s in params], [p > 0.0 for p in ps], row_first,
+            row_stride)
+
+
+def fwd_chain_dropout(x, ws, bs, w_head, b_head, seed, step, layers, ps,
+                      row_first, row_stride, rows=0, waves=0, l1=0, kloop=0,
+                      zero=None):
+    """fwd_chain for a training forward under dropout, still one kernel
+    (GPU only, csrc/fwd_chain_drop.hip).
+
+      h_l = dropout_l(relu(h_{l-1} @ W_l^T + b_l))
+      probs = softmax(h @ W_head^T + b)
+
+    layers / ps: per chain layer, bottom first, its index in the full
+    model (the mask's counter word) and its drop probability; seed, step,
+    row_first, row_stride as linear_fwd_dropout.  The mask is drawn and
+    applied in each layer's epilogue, and the dropped-out tile is the
+    next layer's input.  A layer with p = 0 runs the plain epilogue.
+
+    Returns ([h_l, ...], probs), each bit-identical to
+    linear_fwd_dropout (linear_fwd(relu) where p = 0) -> ... ->
+    head_fwd_fused, or None, with nothing launched and `zero` untouched,
+    outside the kernel's contract: fwd_chain's, plus at least one p > 0
+    and every sample id below 2^32.  Everything else as fwd_chain."""
+    if not _is_gpu(x):
+        return None
+    drop = _chain_drop_args(x, seed, step, layers, ps, row_first, row_stride)
+    if drop is None:
+        return None
+    out = _ext_for(x).fwd_chain_dropout(
+        x, list(ws), list(bs), w_head, b_head, *drop, int(rows), int(waves),
+        int(l1), int(kloop), zero)
+    if not out:
+        return None
+    return out[:-1], out[-1]
+
+
+def fwd_chain_stage_dropout(x, ws, bs, seed, step, layers, ps, row_first,
+                            row_stride, rows=0, waves=0, l1=0, kloop=0):
+    """fwd_chain_stage under dropout (GPU only, the stage arm of
+    csrc/fwd_chain_drop.hip): arguments as fwd_chain_dropout without the
+    head.  Returns [h_l, ...] (the last one, dropped out, is what the
+    stage sends on) or None, with nothing launched, outside the
+    contract."""
+    if not _is_gpu(x):
+        return None
+    drop = _chain_drop_args(x, seed, step, layers, ps, row_first, row_stride)
+    if drop is None:
+        return None
+    out = _ext_for(x).fwd_chain_stage_dropout(
+        x, list(ws), list(bs), *drop, int(rows), int(waves), int(l1),
+        int(kloop))
     return out or None
 
 

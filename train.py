@@ -15,6 +15,7 @@ Single process: python train.py          (dp=1, pp=1, CPU or 1 GPU)
 """
 
 import argparse
+import os
 import sys
 import time
 
@@ -179,6 +180,14 @@ def main():
 
         _F.set_deterministic(True, wgrad=args.deterministic_wgrad)
 
+    if args.dropout > 0 and "SS_FWD_CHAIN_DROPOUT" not in os.environ:
+        # the forward chain under dropout: measured ahead of the per-layer
+        # forward in kernel and step time (profiles/r22_fwd_chain_dropout.md);
+        # SS_FWD_CHAIN_DROPOUT=0 keeps the per-layer forward
+        from shallowspeed_amd.ops import functional as _F
+
+        _F.set_fwd_chain_dropout(True)
+
     if args.tp > 1:
         from shallowspeed_amd.parallel import TPMLP
 
@@ -217,8 +226,6 @@ def main():
     train_ds.load(topo.dp_rank, args.dp)
     val_batch = args.val_batch
     if val_batch is None and args.data_dir:
-        import os
-
         yp = os.path.join(args.data_dir, "y_val.npy")
         if os.path.exists(yp):
             import numpy as np
