@@ -620,6 +620,9 @@ torch::Tensor head_fwd_fused(torch::Tensor x, torch::Tensor w,
 // Fused head backward: dz = (probs - target)/GB, dx = dz @ W (w_t is the
 // transposed bf16 copy [K][C]); with non-empty grad tensors also
 // grad_w += dz^T @ x and grad_b += colsum(dz).  Returns (dz, dx).
+// loss (here and in bwd_chain / bwd_chain_wide): 0 = cross-entropy, 1 =
+// softmax-MSE, dz = probs * (g - rowsum(probs * g)), g = -2 (target -
+// probs)/GB, the bits of head_mse_bwd; metrics then sum squared error.
 std::vector<torch::Tensor> head_bwd_fused(torch::Tensor probs,
                                           torch::Tensor target,
                                           torch::Tensor x, torch::Tensor w_t,
@@ -628,7 +631,7 @@ std::vector<torch::Tensor> head_bwd_fused(torch::Tensor probs,
                                           torch::Tensor grad_b,
                                           int64_t rows_per_block,
                                           std::optional<torch::Tensor> metrics,
-                                          int64_t slots) {
+                                          int64_t slots, int64_t loss) {
     check_bf16(probs, "probs");
     check_bf16(target, "target");
     check_bf16(x, "x");
@@ -636,6 +639,7 @@ std::vector<torch::Tensor> head_bwd_fused(torch::Tensor probs,
     TORCH_CHECK(probs.dim() == 2 && x.dim() == 2 && w_t.dim() == 2,
                 "probs/x/w_t must be 2-D");
     TORCH_CHECK(probs.sizes() == target.sizes(), "shape mismatch");
+    TORCH_CHECK(loss == 0 || loss == 1, "loss must be 0 (xent) or 1 (mse)");
     const int M = x.size(0), K = x.size(1), C = probs.size(1);
     TORCH_CHECK(probs.size(0) == M, "batch mismatch");
     TORCH_CHECK(w_t.size(0) == K && w_t.size(1) == C, "w_t must be [K][C]");
@@ -667,7 +671,7 @@ std::vector<torch::Tensor> head_bwd_fused(torch::Tensor probs,
                                   dx.data_ptr(), gw_p, gb_p, M, K, C,
                                   (float)(1.0 / global_batch),
                                   (int)rows_per_block, met_p, nslots,
-                                  cur_stream()),
+                                  (int)loss, cur_stream()),
                 "shape outside the fused-head contract (C<=16, K%32==0, "
                 "K<=1024): ", M, "x", C, "x", K);
     return {dz, dx};
@@ -723,10 +727,15 @@ std::vector<torch::Tensor> bwd_chain(torch::Tensor probs, torch::Tensor target,
                                      std::vector<torch::Tensor> hs,
                                      std::vector<torch::Tensor> w_ts,
                                      int64_t rows, int64_t waves,
-                                     int64_t w_lds, double dz_scale) {
+                                     int64_t w_lds, double dz_scale,
+                                     int64_t loss) {
     const int64_t n = (int64_t)hs.size();
     const int64_t nw = (int64_t)w_ts.size();
     if (n < 1 || n > SS_BWD_CHAIN_MAX || (nw != n && nw != n - 1)) return {};
+    if (loss != 0 && loss != 1) return {};
+    // arms the squared-error launcher is not built with, refused before
+    // anything is allocated
+    if (loss == 1 && w_lds != 0) return {};
     if (!plain(probs, 2) || !plain(target, 2) || !plain(w_head_t, 2))
         return {};
     if (probs.sizes() != target.sizes()) return {};
@@ -743,7 +752,7 @@ std::vector<torch::Tensor> bwd_chain(torch::Tensor probs, torch::Tensor target,
                       w_head_t.data_ptr(), out[0].data_ptr(), hp, wp, dp,
                       (int)n, dx_p, (int)M, (int)H, (int)C,
                       (float)(1.0 / global_batch), (int)rows, (int)waves,
-                      (int)w_lds, (float)dz_scale, cur_stream()))
+                      (int)w_lds, (float)dz_scale, (int)loss, cur_stream()))
         return {};
     return out;
 }
@@ -1022,10 +1031,12 @@ std::vector<torch::Tensor> bwd_chain_wide(torch::Tensor probs,
                                           double global_batch,
                                           std::vector<torch::Tensor> hs,
                                           std::vector<torch::Tensor> w_ts,
-                                          int64_t rows, int64_t waves) {
+                                          int64_t rows, int64_t waves,
+                                          int64_t loss) {
     const int64_t n = (int64_t)hs.size();
     const int64_t nw = (int64_t)w_ts.size();
     if (n < 1 || n > SS_BWD_CHAIN_MAX || (nw != n && nw != n - 1)) return {};
+    if (loss != 0 && loss != 1) return {};
     if (!plain(probs, 2) || !plain(target, 2) || !plain(w_head_t, 2))
         return {};
     if (probs.sizes() != target.sizes()) return {};
@@ -1044,7 +1055,7 @@ std::vector<torch::Tensor> bwd_chain_wide(torch::Tensor probs,
                            w_head_t.data_ptr(), out[0].data_ptr(), hp, wp, dp,
                            (int)n, dx_p, (int)M, (int)H, (int)C,
                            (float)(1.0 / global_batch), (int)rows, (int)waves,
-                           cur_stream()))
+                           (int)loss, cur_stream()))
         return {};
     return out;
 }
@@ -1410,14 +1421,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           py::arg("probs"), py::arg("target"), py::arg("x"), py::arg("w_t"),
           py::arg("global_batch"), py::arg("grad_w"), py::arg("grad_b"),
           py::arg("rows_per_block") = 0,
-          py::arg("metrics") = py::none(), py::arg("slots") = 0);
+          py::arg("metrics") = py::none(), py::arg("slots") = 0,
+          py::arg("loss") = 0);
     m.def("bwd_chain", &bwd_chain,
           "head backward + 256-wide ReLU dgrads in one launch -> "
           "[dz_head, dz_l..., (dx)], or [] outside the contract",
           py::arg("probs"), py::arg("target"), py::arg("w_head_t"),
           py::arg("global_batch"), py::arg("hs"), py::arg("w_ts"),
           py::arg("rows") = 0, py::arg("waves") = 0, py::arg("w_lds") = 0,
-          py::arg("dz_scale") = 1.0);
+          py::arg("dz_scale") = 1.0, py::arg("loss") = 0);
     m.def("fwd_chain", &fwd_chain,
           "256-wide ReLU layers + fused head forward in one launch -> "
           "[h_l..., probs], or [] outside the contract",
@@ -1464,7 +1476,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "-> [dz_head, dz_l..., (dx)], or [] outside the contract",
           py::arg("probs"), py::arg("target"), py::arg("w_head_t"),
           py::arg("global_batch"), py::arg("hs"), py::arg("w_ts"),
-          py::arg("rows") = 0, py::arg("waves") = 0);
+          py::arg("rows") = 0, py::arg("waves") = 0, py::arg("loss") = 0);
     m.def("head_metrics", &head_metrics,
           "metric totals of (probs, target) into a slotted accumulator",
           py::arg("probs"), py::arg("target"), py::arg("acc"),

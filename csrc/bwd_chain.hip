@@ -42,45 +42,19 @@
 // head: the last stage's, or the whole model's, backward.
 #define BWD_CHAIN_KERNEL bwd_chain_kernel
 #define BWD_CHAIN_HEAD 1
+#define BWD_CHAIN_LAUNCHER ss_bwd_chain_xent
 #define BWD_CHAIN_SCALE(f) ((f) * (dz_scale + ...))
 #include "bwd_chain_kernel.h"
 
-// rows / waves: 0 = the shipped choice (64, 8); (32, 4), (32, 8),
-// (64, 4) and (64, 8) are the measured arms (scripts/microbench_bwd_chain.py,
-// docs/KERNELS.md).  w_lds: 0 = the shipped choice (W^T from L2 into
-// registers), 1 = W^T through LDS, built for (64, 8) only.
-// SS_BWD_CHAIN_ROWS / SS_BWD_CHAIN_WAVES / SS_BWD_CHAIN_WLDS (read once)
-// override the shipped choice for tuning.
-// dz_scale: 1.f runs the unscaled instantiations; any other value the
-// scaled one, which only the shipped arm is built with.
+// loss: 0 = cross-entropy (this file's instantiations), 1 = squared
+// error (bwd_chain_mse.hip's).  Both arms check the same contract first.
 bool ss_bwd_chain(const void* probs, const void* target, const void* Wt_head,
                   void* dz_head, const void* const* h, const void* const* wt,
                   void* const* dz, int nlayers, void* dx, int M, int H, int C,
                   float inv_gb, int rows, int waves, int w_lds,
-                  float dz_scale, hipStream_t st) {
-    if (M < 1 || H != 256 || C < 1 || C > 16 || nlayers < 1 ||
-        nlayers > SS_BWD_CHAIN_MAX)
-        return false;
-    BwdChainLayers L = {};
-    if (!bwd_chain_layers(L, h, wt, dz, nlayers, dx)) return false;
-    bwd_chain_env(rows, waves, w_lds);
-    if (!rows) rows = 64;
-    if (!waves) waves = 8;
-    if (dz_scale != 1.f) {
-        if (rows != 64 || waves != 8 || w_lds != 0) return false;
-        bwd_chain_launch<64, 8, false>(probs, target, Wt_head, dz_head, L,
-                                       nlayers, dx, M, C, inv_gb, st,
-                                       dz_scale);
-        return true;
-    }
-    if (w_lds == 1) {
-        if (rows != 64 || waves != 8) return false;
-        bwd_chain_launch<64, 8, true>(probs, target, Wt_head, dz_head, L,
-                                      nlayers, dx, M, C, inv_gb, st);
-        return true;
-    }
-    return with_chain_arm(rows, waves, [&](auto r, auto nw) {
-        bwd_chain_launch<r.value, nw.value>(probs, target, Wt_head, dz_head,
-                                            L, nlayers, dx, M, C, inv_gb, st);
-    });
+                  float dz_scale, int loss, hipStream_t st) {
+    if (loss != 0 && loss != 1) return false;
+    return (loss ? ss_bwd_chain_mse : ss_bwd_chain_xent)(
+        probs, target, Wt_head, dz_head, h, wt, dz, nlayers, dx, M, H, C,
+        inv_gb, rows, waves, w_lds, dz_scale, st);
 }

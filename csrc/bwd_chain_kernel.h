@@ -4,7 +4,15 @@
 // BWD_CHAIN_KERNEL (the kernel's name), BWD_CHAIN_HEAD (1: the chain
 // starts at the classifier head, 0: the stage arm, from a stored dout)
 // and BWD_CHAIN_SCALE(f) (the arm's text of f · dz_scale), for the
-// reasons given in fwd_chain_kernel.h.
+// reasons given in fwd_chain_kernel.h.  A headed arm also defines
+// BWD_CHAIN_LAUNCHER (the name of its host launcher) and may define
+// BWD_CHAIN_MSE 1 (bwd_chain_mse.hip): the head step then computes the
+// softmax-MSE dz, whose row sum every lane of the wave takes part in
+// (head_dev.h: head_mse_dz_elem); nothing else differs.
+
+#ifndef BWD_CHAIN_MSE
+#define BWD_CHAIN_MSE 0
+#endif
 
 #include "chain_dev.h"
 #include "launchers.h"
@@ -123,6 +131,23 @@ void BWD_CHAIN_KERNEL(
         for (int e = tid; e < R * 16; e += NT) {
             const int r = e >> 4, c = e & 15;
             ushort bits = 0;
+#if BWD_CHAIN_MSE
+            // whole waves per trip: the row sum is a cross-lane step, so
+            // the guard stands around the loads and the store only
+            static_assert(R * 16 % NT == 0, "whole waves per trip");
+            const bool live = c < C && row0 + r < M;
+            const long gi = (long)(row0 + r) * C + c;
+            __bf16 pb = (__bf16)0.f, tb = (__bf16)0.f;
+            if (live) {
+                pb = probs[gi];
+                tb = target[gi];
+            }
+            const __bf16 o = head_mse_dz_elem(pb, tb, inv_gb);
+            if (live) {
+                dz_head[gi] = o;
+                bits = bf_bits(o);
+            }
+#else
             if (c < C && row0 + r < M) {
                 const long gi = (long)(row0 + r) * C + c;
                 const __bf16 o =
@@ -130,6 +155,7 @@ void BWD_CHAIN_KERNEL(
                 dz_head[gi] = o;
                 bits = bf_bits(o);
             }
+#endif
             dzs[r][c] = bits;
         }
         __syncthreads();
@@ -299,3 +325,52 @@ void bwd_chain_env(int& rows, int& waves, int& w_lds) {
 }
 
 }  // namespace
+
+#if BWD_CHAIN_HEAD
+// This loss's arm of ss_bwd_chain (launchers.h), which selects it.
+// rows / waves: 0 = the shipped choice (64, 8); (32, 4), (32, 8),
+// (64, 4) and (64, 8) are the measured arms (scripts/microbench_bwd_chain.py,
+// docs/KERNELS.md).  w_lds: 0 = the shipped choice (W^T from L2 into
+// registers), 1 = W^T through LDS, built for (64, 8) and cross-entropy
+// only.
+// SS_BWD_CHAIN_ROWS / SS_BWD_CHAIN_WAVES / SS_BWD_CHAIN_WLDS (read once)
+// override the shipped choice for tuning.
+// dz_scale: 1.f runs the unscaled instantiations; any other value the
+// scaled one, which only the shipped arm is built with.
+bool BWD_CHAIN_LAUNCHER(const void* probs, const void* target,
+                        const void* Wt_head, void* dz_head,
+                        const void* const* h, const void* const* wt,
+                        void* const* dz, int nlayers, void* dx, int M, int H,
+                        int C, float inv_gb, int rows, int waves, int w_lds,
+                        float dz_scale, hipStream_t st) {
+    if (M < 1 || H != 256 || C < 1 || C > 16 || nlayers < 1 ||
+        nlayers > SS_BWD_CHAIN_MAX)
+        return false;
+    BwdChainLayers L = {};
+    if (!bwd_chain_layers(L, h, wt, dz, nlayers, dx)) return false;
+    bwd_chain_env(rows, waves, w_lds);
+    if (!rows) rows = 64;
+    if (!waves) waves = 8;
+    if (dz_scale != 1.f) {
+        if (rows != 64 || waves != 8 || w_lds != 0) return false;
+        bwd_chain_launch<64, 8, false>(probs, target, Wt_head, dz_head, L,
+                                       nlayers, dx, M, C, inv_gb, st,
+                                       dz_scale);
+        return true;
+    }
+    if (w_lds == 1) {
+#if BWD_CHAIN_MSE
+        return false;
+#else
+        if (rows != 64 || waves != 8) return false;
+        bwd_chain_launch<64, 8, true>(probs, target, Wt_head, dz_head, L,
+                                      nlayers, dx, M, C, inv_gb, st);
+        return true;
+#endif
+    }
+    return with_chain_arm(rows, waves, [&](auto r, auto nw) {
+        bwd_chain_launch<r.value, nw.value>(probs, target, Wt_head, dz_head,
+                                            L, nlayers, dx, M, C, inv_gb, st);
+    });
+}
+#endif

@@ -49,184 +49,27 @@
     __attribute__((target("no-packed-fp32-ops"))), apply_to = function)
 #endif
 
-#include "chain_wide.h"
+// The kernel's text and its launch are bwd_chain_wide_kernel.h; this
+// file compiles the cross-entropy arm (bwd_chain_wide_mse.hip the
+// squared-error one).
+#define BWD_WIDE_KERNEL bwd_chain_wide_kernel
+#define BWD_WIDE_LAUNCHER ss_bwd_chain_wide_xent
+#define BWD_WIDE_MSE 0
+#include "bwd_chain_wide_kernel.h"
 
-namespace {
-
-// The layers of one launch, top first.  Passed BY VALUE: nothing to
-// upload, nothing to keep alive, and legal under graph capture.
-struct BwdWideLayers {
-    const void* h[SS_BWD_CHAIN_MAX];   // post-ReLU output, the mask source
-    const void* wt[SS_BWD_CHAIN_MAX];  // W^T [H][H], or null: chain ends
-    void* dz[SS_BWD_CHAIN_MAX];        // masked gradient out
-};
-
-template <int HH, int R, int NW>
-__global__ __launch_bounds__(NW * 64)
-void bwd_chain_wide_kernel(
-    const __bf16* __restrict__ probs,    // [M][C]
-    const __bf16* __restrict__ target,   // [M][C]
-    const __bf16* __restrict__ Wt_head,  // [H][C]
-    __bf16* __restrict__ dz_head,        // [M][C]
-    const BwdWideLayers L, int nlayers,
-    __bf16* __restrict__ dx,             // [M][H] or null
-    int M, int C, float inv_gb) {
-    // the names CHAIN_LAYER_MMA_AHEAD, CHAIN_ACC_TO_TILE and
-    // CHAIN_FOR_PIECES read
-    constexpr int H = HH;
-    constexpr int NT = NW * 64;
-    constexpr int LDT = H + 8;        // padded tile row (bf16)
-    constexpr int PPR = H / 8;        // 16-B pieces per tile row
-    constexpr int NP = R * PPR / NT;  // pieces per thread
-    constexpr int FM = R / 16;        // 16-row fragments per tile
-    constexpr int WN = H / NW;        // columns per wave
-    constexpr int FN = WN / 16;
-    constexpr int NSTEP = H / 32;     // K-steps of a layer
-    constexpr int HC = H < 256 ? H : 256;  // W_head^T rows per staged chunk
-    static_assert(WN % 16 == 0 && FN >= 1 && R % 16 == 0, "fragment split");
-    static_assert(R * PPR % NT == 0 && NP >= 1, "piece mapping");
-    static_assert(NT >= HC && H % HC == 0, "one thread per W_head^T row");
-    static_assert(NSTEP > CHAIN_B_AHEAD, "K loop");
-    // every built arm keeps B three K-steps ahead: accumulators + the ring
-    // of four B sets + the A fragments + the mask source that is in
-    // flight under the K loop leave some thirty registers for addresses
-    static_assert(4 * FM * FN + 16 * FN + 4 * FM + 4 * NP + 30 <=
-                      wide_reg_budget(NW),
-                  "register budget of CHAIN_LAYER_MMA_AHEAD");
-
-    __shared__ __attribute__((aligned(16))) ushort tile[R][LDT];
-    __shared__ __attribute__((aligned(16))) ushort wts[HC][16];
-    __shared__ __attribute__((aligned(16))) ushort dzs[R][16];
-
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = tid >> 6;
-    const int lrow = lane & 15;
-    const int kch = lane >> 4;
-    const int row0 = blockIdx.x * R;
-
-    // mask source of the next mask pass, issued a phase ahead (rows past
-    // M as zeros: they mask to zero and are never stored)
-    bf16x8 hm[NP];
-    auto load_mask = [&](int l) {
-        const gbf16* h = (const gbf16*)L.h[l];
-        CHAIN_FOR_PIECES(i, r, col) {
-            hm[i] = zero8();
-            if (row0 + r < M)
-                hm[i] = *(const gbf16x8*)&h[(long)(row0 + r) * H + col];
-        }
-    };
-    load_mask(0);
-
-    // ---- head: dz_head of the tile, stored and kept as the MFMA A
-    // operand (class index = k slot, k >= C zero)
-    for (int e = tid; e < R * 16; e += NT) {
-        const int r = e >> 4, c = e & 15;
-        ushort bits = 0;
-        if (c < C && row0 + r < M) {
-            const long gi = (long)(row0 + r) * C + c;
-            const __bf16 o = head_dz_elem(probs[gi], target[gi], inv_gb);
-            dz_head[gi] = o;
-            bits = bf_bits(o);
-        }
-        dzs[r][c] = bits;
-    }
-    // dh of the top layer, HC columns per staged chunk of W_head^T
-    for (int k0 = 0; k0 < H; k0 += HC) {
-        if (k0 > 0) __syncthreads();  // every wave has read the last chunk
-        HEAD_STAGE_WT(HC, wts, Wt_head, k0, HC, C, tid)
-        __syncthreads();  // first chunk: dzs as well
-        for (int idx = wave; idx < FM * (HC / 16); idx += NW) {
-            const int rg = idx % FM, ct = idx / FM;
-            HEAD_DX_FRAG(acc, dzs, wts, rg, ct, lrow, kch);
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-                tile[rg * 16 + kch * 4 + r][k0 + ct * 16 + lrow] =
-                    bf_bits(f2bf(acc[r]));
-        }
-    }
-    __syncthreads();
-
-    // ---- the ReLU layers: the tile holds dh of layer l
-    for (int l = 0; l < nlayers; ++l) {
-        // mask pass: dz_l replaces dh in the tile and goes out as 16-B
-        // row-contiguous stores (a thread touches only its own pieces,
-        // so no barrier inside the pass)
-        gbf16* const dzo = (gbf16*)L.dz[l];
-        CHAIN_FOR_PIECES(i, r, col) {
-            bf16x8 v = *(const bf16x8*)&tile[r][col];
-#pragma unroll
-            for (int e = 0; e < 8; ++e)
-                if (!(bf2f(hm[i][e]) > 0.f)) v[e] = (__bf16)0.f;
-            *(bf16x8*)&tile[r][col] = v;
-            if (row0 + r < M)
-                *(gbf16x8*)&dzo[(long)(row0 + r) * H + col] = v;
-        }
-        const gbf16* const wt = (const gbf16*)L.wt[l];
-        if (wt == nullptr) break;  // block-uniform: the chain ends
-        if (l + 1 < nlayers) load_mask(l + 1);
-        __syncthreads();
-
-        // dh_{l-1} = dz_l · W_l, W^T straight from L2
-        f32x4 acc[FM][FN];
-#pragma unroll
-        for (int i = 0; i < FM; ++i)
-#pragma unroll
-            for (int j = 0; j < FN; ++j) acc[i][j] = {0.f, 0.f, 0.f, 0.f};
-        CHAIN_LAYER_MMA_AHEAD(acc, tile, wt)
-        __syncthreads();  // every wave has read the dz tile
-        CHAIN_ACC_TO_TILE(acc, tile, )
-        __syncthreads();
-    }
-
-    // every layer's dgrad was in the chain: the tile is dx
-    if (dx != nullptr) {
-        CHAIN_FOR_PIECES(i, r, col) {
-            if (row0 + r < M)
-                *(bf16x8*)&dx[(long)(row0 + r) * H + col] =
-                    *(const bf16x8*)&tile[r][col];
-        }
-    }
-}
-
-}  // namespace
-
-// rows / waves: 0 = the shipped choice (docs/KERNELS.md, "Chain kernels,
-// wide"); any other pair must be one of with_chain_wide_arm's.
+// loss: 0 = cross-entropy (this file's instantiations), 1 = squared
+// error (bwd_chain_wide_mse.hip's).  Both arms check the same contract
+// first.
 bool ss_bwd_chain_wide(const void* probs, const void* target,
                        const void* Wt_head, void* dz_head,
                        const void* const* h, const void* const* wt,
                        void* const* dz, int nlayers, void* dx, int M, int H,
-                       int C, float inv_gb, int rows, int waves,
+                       int C, float inv_gb, int rows, int waves, int loss,
                        hipStream_t st) {
-    if (M < 1 || M > INT32_MAX - 64 || (H != 128 && H != 512) || C < 1 ||
-        C > 16 || nlayers < 1 || nlayers > SS_BWD_CHAIN_MAX)
-        return false;
-    if (!aligned16(probs) || !aligned16(target) || !aligned16(Wt_head) ||
-        !aligned16(dz_head))
-        return false;
-    BwdWideLayers L = {};
-    for (int l = 0; l < nlayers; ++l) {
-        const bool last = l + 1 == nlayers;
-        if (!aligned16(h[l]) || !aligned16(dz[l])) return false;
-        if (!last && !aligned16(wt[l])) return false;
-        if (last && (wt[l] != nullptr) != (dx != nullptr)) return false;
-        if (last && dx && !(aligned16(wt[l]) && aligned16(dx))) return false;
-        L.h[l] = h[l];
-        L.wt[l] = wt[l];
-        L.dz[l] = dz[l];
-    }
-    chain_wide_shipped(H, M, rows, waves);
-    auto launch = [&](auto hh, auto r, auto nw) {
-        constexpr int HH = hh.value, R = r.value, NW = nw.value;
-        hipLaunchKernelGGL((bwd_chain_wide_kernel<HH, R, NW>),
-                           dim3(cdiv(M, R)), dim3(NW * 64), 0, st,
-                           (const __bf16*)probs, (const __bf16*)target,
-                           (const __bf16*)Wt_head, (__bf16*)dz_head, L,
-                           nlayers, (__bf16*)dx, M, C, inv_gb);
-    };
-    return H == 128 ? with_chain_wide_arm<128>(rows, waves, launch)
-                    : with_chain_wide_arm<512>(rows, waves, launch);
+    if (loss != 0 && loss != 1) return false;
+    return (loss ? ss_bwd_chain_wide_mse : ss_bwd_chain_wide_xent)(
+        probs, target, Wt_head, dz_head, h, wt, dz, nlayers, dx, M, H, C,
+        inv_gb, rows, waves, st);
 }
 
 #if defined(__HIP_DEVICE_COMPILE__)

@@ -31,6 +31,29 @@ __device__ __forceinline__ __bf16 head_dz_elem(__bf16 pb, __bf16 tb,
     return f2bf((bf2f(pb) - bf2f(tb)) * inv_gb);
 }
 
+// dz of one head element under the softmax-MSE loss:
+//     g = -2 (t - s) / GB ;  dz = bf16(s · (g - Σ_c s·g))
+// for the head tile layout of the backward kernels, thread e -> (row
+// e >> 4, class e & 15): the 16 classes of a row sit in 16 adjacent lanes
+// of one wave, so Σ_c is the xor tree over offsets 8, 4, 2, 1, with no
+// LDS and no barrier.  EVERY lane of the wave must call this; a lane past
+// C or past M passes pb = tb = +0 and adds 0.f + 0·(-0) = +0 to its row.
+// The bf16 is head_mse_bwd_kernel's (elementwise.hip): the same
+// expressions in the same order (a per-lane partial that starts at 0.f,
+// so a product of -0 enters the tree as +0 there and here, contracted to
+// an FMA or not), and that kernel's wave_sum is this tree after two steps
+// (offsets 32, 16) that for C <= 16 only add +0.
+__device__ __forceinline__ __bf16 head_mse_dz_elem(__bf16 pb, __bf16 tb,
+                                                   float inv_gb) {
+    const float s = bf2f(pb);
+    const float g = -2.f * (bf2f(tb) - s) * inv_gb;
+    float dot = 0.f;
+    dot += s * g;
+#pragma unroll
+    for (int off = 8; off > 0; off >>= 1) dot += __shfl_xor(dot, off, 64);
+    return f2bf(s * (g - dot));
+}
+
 // W^T rows [k0, k0 + kc) of the head, zero-padded to 16 classes, into
 // wts[KC][16] (LDS): thread k < KC stages row k, rows past kc as zeros.
 #define HEAD_STAGE_WT(KC, wts, Wt, k0, kc, C, tid)                           \

@@ -158,10 +158,27 @@ int ss_wgrad_group_ordered_plan(const WgradProblem* problems, int n,
 bool ss_head_fwd_fused(const void* x, const void* W, const void* bias,
                        void* probs, int M, int K, int C, int rows_per_block,
                        hipStream_t stream);
+// loss (here and in the backward chains below): 0 = softmax
+// cross-entropy, dz = (p − t)/GB; 1 = softmax squared error, dz =
+// p·(g − Σ_c p·g) with g = −2(t − p)/GB; anything else returns false.
+// Each loss's kernels live in a translation unit of their own, behind
+// the *_xent / *_mse launchers, which take the same arguments and check
+// the same contract; callers go through the one that takes `loss`.
 bool ss_head_bwd_fused(const void* probs, const void* target, const void* x,
                        const void* Wt, void* dz, void* dx, void* gW, void* gb,
                        int M, int K, int C, float inv_gb, int rows_per_block,
-                       void* metrics, int slots, hipStream_t stream);
+                       void* metrics, int slots, int loss,
+                       hipStream_t stream);
+bool ss_head_bwd_fused_xent(const void* probs, const void* target,
+                            const void* x, const void* Wt, void* dz, void* dx,
+                            void* gW, void* gb, int M, int K, int C,
+                            float inv_gb, int rows_per_block, void* metrics,
+                            int slots, hipStream_t stream);  // head.hip
+bool ss_head_bwd_fused_mse(const void* probs, const void* target,
+                           const void* x, const void* Wt, void* dz, void* dx,
+                           void* gW, void* gb, int M, int K, int C,
+                           float inv_gb, int rows_per_block, void* metrics,
+                           int slots, hipStream_t stream);  // head_mse.hip
 bool ss_head_metrics(const void* probs, const void* target, void* acc,
                      int slots, int M, int C, int kind, hipStream_t stream);
 
@@ -176,7 +193,21 @@ bool ss_bwd_chain(const void* probs, const void* target, const void* Wt_head,
                   void* dz_head, const void* const* h, const void* const* wt,
                   void* const* dz, int nlayers, void* dx, int M, int H, int C,
                   float inv_gb, int rows, int waves, int w_lds,
-                  float dz_scale, hipStream_t stream);
+                  float dz_scale, int loss, hipStream_t stream);
+// bwd_chain.hip; every arm
+bool ss_bwd_chain_xent(const void* probs, const void* target,
+                       const void* Wt_head, void* dz_head,
+                       const void* const* h, const void* const* wt,
+                       void* const* dz, int nlayers, void* dx, int M, int H,
+                       int C, float inv_gb, int rows, int waves, int w_lds,
+                       float dz_scale, hipStream_t stream);
+// bwd_chain_mse.hip; no W-through-LDS arm (w_lds == 1 returns false)
+bool ss_bwd_chain_mse(const void* probs, const void* target,
+                      const void* Wt_head, void* dz_head,
+                      const void* const* h, const void* const* wt,
+                      void* const* dz, int nlayers, void* dx, int M, int H,
+                      int C, float inv_gb, int rows, int waves, int w_lds,
+                      float dz_scale, hipStream_t stream);
 // The stage arm, for a pipeline stage with no head: the chain starts
 // from dout [M][256], the received gradient of the top layer's output,
 // 16-byte aligned.  Everything else as ss_bwd_chain, except that the
@@ -259,8 +290,20 @@ bool ss_bwd_chain_wide(const void* probs, const void* target,
                        const void* Wt_head, void* dz_head,
                        const void* const* h, const void* const* wt,
                        void* const* dz, int nlayers, void* dx, int M, int H,
-                       int C, float inv_gb, int rows, int waves,
+                       int C, float inv_gb, int rows, int waves, int loss,
                        hipStream_t stream);
+bool ss_bwd_chain_wide_xent(const void* probs, const void* target,
+                            const void* Wt_head, void* dz_head,
+                            const void* const* h, const void* const* wt,
+                            void* const* dz, int nlayers, void* dx, int M,
+                            int H, int C, float inv_gb, int rows, int waves,
+                            hipStream_t stream);  // bwd_chain_wide.hip
+bool ss_bwd_chain_wide_mse(const void* probs, const void* target,
+                           const void* Wt_head, void* dz_head,
+                           const void* const* h, const void* const* wt,
+                           void* const* dz, int nlayers, void* dx, int M,
+                           int H, int C, float inv_gb, int rows, int waves,
+                           hipStream_t stream);  // bwd_chain_wide_mse.hip
 
 // ---- fused_mlp.hip
 bool ss_fused_mlp_fwd(const void* x, const void* desc, int M, int in_dim,

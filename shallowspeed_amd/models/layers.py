@@ -568,8 +568,9 @@ class Sequential(Module):
         # deferred path — round-1 deferred all grads to OptimizerStep).
         self._flush_in_backward = False
 
-    # Linear(activation=None) -> SoftmaxXent at the end of the chain may
-    # run as the fused head kernels (csrc/head.hip); subclasses whose
+    # Linear(activation=None) -> SoftmaxXent (or SoftmaxMSE, see
+    # _head_pair) at the end of the chain may run as the fused head
+    # kernels (csrc/head.hip, csrc/head_mse.hip); subclasses whose
     # last Linear is not a plain one opt out.
     _fuse_head = True
 
@@ -602,13 +603,16 @@ class Sequential(Module):
         return self._has_dropout
 
     def _head_pair(self):
-        """(last Linear, SoftmaxXent head) when the chain ends in that
-        pair, else None."""
+        """(last Linear, loss head) when the chain ends in a plain Linear
+        under a head the fused kernels serve, else None: SoftmaxXent, and
+        SoftmaxMSE while F.head_mse_fused() is on (the backward kernels
+        take the head's `kind` as their loss)."""
         if not self._fuse_head or len(self.layers) < 2:
             return None
         lin, head = self.layers[-2], self.layers[-1]
-        if type(head) is SoftmaxXent and type(lin) is Linear \
-                and lin.activation is None:
+        fused = type(head) is SoftmaxXent \
+            or type(head) is SoftmaxMSE and F.head_mse_fused()
+        if fused and type(lin) is Linear and lin.activation is None:
             return lin, head
         return None
 
@@ -927,7 +931,8 @@ class Sequential(Module):
         dz, dx = F.head_bwd_fused(
             s, target, x, lin.weight.compute_t(), head.global_batch_size,
             lin.weight.grad if in_kernel else None,
-            lin.bias.grad if in_kernel else None, metrics=acc)
+            lin.bias.grad if in_kernel else None, metrics=acc,
+            loss=head.kind)
         if lin._defer_wgrad:
             lin._wgrad_pending.append((dz, x, None))
             if len(lin._wgrad_pending) >= lin._wgrad_window:
@@ -1042,8 +1047,9 @@ class Sequential(Module):
                     for l, (_, dg) in zip(chain, plan) if dg]
             args = (s, target, lin.weight.compute_t(),
                     head.global_batch_size, hs, w_ts)
-            res = launch(*args) if launch else \
-                F.bwd_chain(*args, dz_scale=chain[0].dz_scale())
+            res = launch(*args, loss=head.kind) if launch else \
+                F.bwd_chain(*args, dz_scale=chain[0].dz_scale(),
+                            loss=head.kind)
             if res is None:
                 return False, None
             dz_head, dzs, dx = res

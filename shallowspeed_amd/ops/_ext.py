@@ -81,7 +81,9 @@ def build_ext(verbose=True):
         os.path.join(src_dir, "fp8.hip"),
         os.path.join(src_dir, "elementwise.hip"),
         os.path.join(src_dir, "head.hip"),
+        os.path.join(src_dir, "head_mse.hip"),
         os.path.join(src_dir, "bwd_chain.hip"),
+        os.path.join(src_dir, "bwd_chain_mse.hip"),
         os.path.join(src_dir, "fwd_chain.hip"),
         os.path.join(src_dir, "bwd_chain_stage.hip"),
         os.path.join(src_dir, "fwd_chain_stage.hip"),
@@ -93,6 +95,7 @@ def build_ext(verbose=True):
         os.path.join(src_dir, "fused_mlp_taper.hip"),
         os.path.join(src_dir, "fwd_chain_wide.hip"),
         os.path.join(src_dir, "bwd_chain_wide.hip"),
+        os.path.join(src_dir, "bwd_chain_wide_mse.hip"),
     ]
     mod = load(
         name=_EXT_NAME,

@@ -131,6 +131,33 @@ def head_wgrad_fused() -> bool:
     return _HEAD_WGRAD_FUSED
 
 
+_HEAD_MSE_FUSED = None
+# the `loss` argument of head_bwd_fused / bwd_chain / bwd_chain_wide
+_HEAD_LOSS = {"xent": 0, "mse": 1}
+
+
+def set_head_mse_fused(flag: bool):
+    """Let a model that ends in Linear -> SoftmaxMSE take the fused head,
+    and with it every plan that hangs off the head pair (forward chain,
+    plain and under dropout, backward chain at 256 / 128 / 512, grouped
+    and ordered wgrads): the backward kernels then run their
+    squared-error arm (loss="mse"), whose dz has the bits of
+    head_softmax_mse_bwd.  Default OFF: the softmax-MSE head keeps the
+    per-layer path.  SS_HEAD_MSE_FUSED=1 (read once) turns it on
+    (profiles/r23_head_mse.md)."""
+    global _HEAD_MSE_FUSED
+    _HEAD_MSE_FUSED = bool(flag)
+
+
+def head_mse_fused() -> bool:
+    global _HEAD_MSE_FUSED
+    if _HEAD_MSE_FUSED is None:
+        import os
+
+        _HEAD_MSE_FUSED = os.environ.get("SS_HEAD_MSE_FUSED", "0") == "1"
+    return _HEAD_MSE_FUSED
+
+
 _BWD_CHAIN = None
 
 
@@ -736,7 +763,7 @@ def head_softmax_xent_bwd(probs, target, global_batch):
 
 
 def head_fused_ok(x, linear) -> bool:
-    """True when `linear` (the Linear feeding a SoftmaxXent head) and
+    """True when `linear` (the Linear feeding a fused loss head) and
     its input meet the launch contract of the fused head kernels:
     GPU, bf16, no activation, no fp8 forward, out <= 16, in % 32 == 0,
     in <= 1024."""
@@ -758,7 +785,7 @@ def head_fwd_fused(x, w, b):
 
 
 def head_bwd_fused(probs, target, x, w_t, global_batch, grad_w=None,
-                   grad_b=None, metrics=None):
+                   grad_b=None, metrics=None, loss="xent"):
     """(dz, dx) of the fused head in one kernel: dz = (probs - t)/GB,
     dx = dz @ W — bit-identical to head_softmax_xent_bwd ->
     linear_dgrad.  With grad_w (and grad_b) given, the same kernel also
@@ -766,18 +793,22 @@ def head_bwd_fused(probs, target, x, w_t, global_batch, grad_w=None,
     atomics (one set per block, at most 256 blocks).  With `metrics` (an
     accumulator of new_metrics_acc) it also adds the cross-entropy
     metric totals of (probs, target) — same values as head_metrics, no
-    second launch; dz and dx keep their bits."""
+    second launch; dz and dx keep their bits.
+
+    loss="mse": the softmax-MSE head, dz = probs * (g - rowsum(probs *
+    g)) with g = -2 (t - probs)/GB, bit-identical to head_softmax_mse_bwd
+    (the row sum is taken inside the kernel); the metrics are then the
+    squared-error ones.  Everything else is the same."""
     empty = torch.Tensor()
     args = (probs, target, x, w_t, float(global_batch),
             grad_w if grad_w is not None else empty,
             grad_b if grad_b is not None else empty)
-    if metrics is None:
-        return tuple(_ext_for(probs).head_bwd_fused(*args))
-    return tuple(_ext_for(probs).head_bwd_fused(*args, 0, metrics, 0))
+    return tuple(_ext_for(probs).head_bwd_fused(*args, 0, metrics, 0,
+                                                _HEAD_LOSS[loss]))
 
 
 def bwd_chain(probs, target, w_head_t, global_batch, hs, w_ts, rows=0,
-              waves=0, w_lds=0, dz_scale=1.0):
+              waves=0, w_lds=0, dz_scale=1.0, loss="xent"):
     """Head backward plus the ReLU-layer data gradients below it in one
     kernel (GPU only, csrc/bwd_chain.hip).
 
@@ -799,13 +830,16 @@ def bwd_chain(probs, target, w_head_t, global_batch, hs, w_ts, rows=0,
     kept dz_l element is bf16(dh · dz_scale), bit-identical to
     relu_bwd(dh, h_l, scale=dz_scale).  One scale per launch; built for
     the shipped arm only, so another arm returns None.  dz_scale == 1
-    runs the unscaled kernel."""
+    runs the unscaled kernel.
+
+    loss="mse": dz_head is the softmax-MSE one, bit-identical to
+    head_softmax_mse_bwd; the layers below are the same.  No w_lds arm."""
     if not _is_gpu(probs):
         return None
     out = _ext_for(probs).bwd_chain(probs, target, w_head_t,
                                     float(global_batch), list(hs), list(w_ts),
                                     int(rows), int(waves), int(w_lds),
-                                    float(dz_scale))
+                                    float(dz_scale), _HEAD_LOSS[loss])
     if not out:
         return None
     n = len(hs)
@@ -992,10 +1026,10 @@ def fwd_chain_wide(x, ws, bs, w_head, b_head, rows=0, waves=0):
 
 
 def bwd_chain_wide(probs, target, w_head_t, global_batch, hs, w_ts, rows=0,
-                   waves=0):
+                   waves=0, loss="xent"):
     """bwd_chain at hidden width H = 128 or 512 (GPU only,
     csrc/bwd_chain_wide.hip); H is w_head_t's row count.  hs / w_ts as
-    bwd_chain.  No dropout scale.
+    bwd_chain, loss as there.  No dropout scale.
 
     Returns (dz_head, [dz_l, ...], dx or None), each bit-identical to
     head_bwd_fused -> relu_bwd -> linear_dgrad -> ..., or None, with
@@ -1005,7 +1039,8 @@ def bwd_chain_wide(probs, target, w_head_t, global_batch, hs, w_ts, rows=0,
         return None
     out = _ext_for(probs).bwd_chain_wide(probs, target, w_head_t,
                                          float(global_batch), list(hs),
-                                         list(w_ts), int(rows), int(waves))
+                                         list(w_ts), int(rows), int(waves),
+                                         _HEAD_LOSS[loss])
     if not out:
         return None
     n = len(hs)

@@ -188,6 +188,15 @@ def main():
 
         _F.set_fwd_chain_dropout(True)
 
+    if args.loss == "mse" and "SS_HEAD_MSE_FUSED" not in os.environ:
+        # the fused head and the chain kernels under the softmax-MSE head:
+        # measured ahead of the per-layer step by far more than five times
+        # the run-to-run spread (profiles/r23_head_mse.md);
+        # SS_HEAD_MSE_FUSED=0 keeps the per-layer step
+        from shallowspeed_amd.ops import functional as _F
+
+        _F.set_head_mse_fused(True)
+
     if args.tp > 1:
         from shallowspeed_amd.parallel import TPMLP
 
