@@ -984,14 +984,21 @@ std::vector<torch::Tensor> fwd_chain_stage_dropout(
 // H read from w_head.  The first layer always streams x.  Returns
 // [h_0, ..., h_{n-1}, probs], or an EMPTY list with nothing allocated or
 // launched outside the kernel's contract.
-std::vector<torch::Tensor> fwd_chain_wide(torch::Tensor x,
-                                          std::vector<torch::Tensor> ws,
-                                          std::vector<torch::Tensor> bs,
-                                          torch::Tensor w_head,
-                                          torch::Tensor b_head, int64_t rows,
-                                          int64_t waves) {
+// drop != null: the arm under dropout (fwd_chain_wide_dropout below),
+// refused as well when no layer of the launch draws a mask or the last row
+// is no 32-bit sample id.
+static std::vector<torch::Tensor> fwd_chain_wide_any(
+    const torch::Tensor& x, const std::vector<torch::Tensor>& ws,
+    const std::vector<torch::Tensor>& bs, const torch::Tensor& w_head,
+    const torch::Tensor& b_head, int64_t rows, int64_t waves,
+    const FwdChainDrop* drop = nullptr) {
     const int64_t n = (int64_t)ws.size();
     if (n < 1 || n > SS_FWD_CHAIN_MAX || (int64_t)bs.size() != n) return {};
+    if (drop && (drop->on == 0 || (drop->on >> n) != 0 || x.dim() != 2 ||
+                 (int64_t)drop->row_first +
+                         (x.size(0) - 1) * (int64_t)drop->row_stride >
+                     (int64_t)UINT_MAX))
+        return {};
     if (!plain(x, 2) || !plain(w_head, 2) || !plain(b_head, 1)) return {};
     const int64_t M = x.size(0), K0 = x.size(1);
     const int64_t C = w_head.size(0), H = w_head.size(1);
@@ -1014,17 +1021,52 @@ std::vector<torch::Tensor> fwd_chain_wide(torch::Tensor x,
         hp[l] = out.back().data_ptr();
     }
     out.push_back(torch::empty({M, C}, x.options()));
-    if (!ss_fwd_chain_wide(x.data_ptr(), wp, bp, hp, (int)n,
-                           w_head.data_ptr(), b_head.data_ptr(),
-                           out.back().data_ptr(), (int)M, (int)K0, (int)H,
-                           (int)C, (int)rows, (int)waves, cur_stream()))
+    if (!(drop ? ss_fwd_chain_wide_dropout(
+                     x.data_ptr(), wp, bp, hp, (int)n, w_head.data_ptr(),
+                     b_head.data_ptr(), out.back().data_ptr(), (int)M,
+                     (int)K0, (int)H, (int)C, (int)rows, (int)waves, *drop,
+                     cur_stream())
+               : ss_fwd_chain_wide(x.data_ptr(), wp, bp, hp, (int)n,
+                                   w_head.data_ptr(), b_head.data_ptr(),
+                                   out.back().data_ptr(), (int)M, (int)K0,
+                                   (int)H, (int)C, (int)rows, (int)waves,
+                                   cur_stream())))
         return {};
     return out;
 }
 
+std::vector<torch::Tensor> fwd_chain_wide(torch::Tensor x,
+                                          std::vector<torch::Tensor> ws,
+                                          std::vector<torch::Tensor> bs,
+                                          torch::Tensor w_head,
+                                          torch::Tensor b_head, int64_t rows,
+                                          int64_t waves) {
+    return fwd_chain_wide_any(x, ws, bs, w_head, b_head, rows, waves);
+}
+
+// Wide forward chain under dropout (fwd_chain_wide_drop.hip):
+// fwd_chain_wide with the mask of layer l (counter word layers[l],
+// thrs[l], scales[l]) in its epilogue; a layer with drops[l] false runs
+// the plain epilogue.  Same result list, EMPTY with nothing allocated or
+// launched outside the contract.
+std::vector<torch::Tensor> fwd_chain_wide_dropout(
+    torch::Tensor x, std::vector<torch::Tensor> ws,
+    std::vector<torch::Tensor> bs, torch::Tensor w_head, torch::Tensor b_head,
+    int64_t key0, int64_t key1, int64_t step, std::vector<int64_t> layers,
+    std::vector<int64_t> thrs, std::vector<double> scales,
+    std::vector<bool> drops, int64_t row_first, int64_t row_stride,
+    int64_t rows, int64_t waves) {
+    FwdChainDrop d;
+    if (!fwd_chain_drop_block(d, (int64_t)ws.size(), key0, key1, step, layers,
+                              thrs, scales, drops, row_first, row_stride))
+        return {};
+    return fwd_chain_wide_any(x, ws, bs, w_head, b_head, rows, waves, &d);
+}
+
 // Wide backward chain (bwd_chain_wide.hip): bwd_chain at H = 128 or 512,
 // H read from w_head_t.  Returns [dz_head, dz_0, ..., dz_{n-1}(, dx)], or
-// an EMPTY list with nothing allocated or launched.
+// an EMPTY list with nothing allocated or launched.  dz_scale as
+// bwd_chain's, built for every arm.
 std::vector<torch::Tensor> bwd_chain_wide(torch::Tensor probs,
                                           torch::Tensor target,
                                           torch::Tensor w_head_t,
@@ -1032,7 +1074,7 @@ std::vector<torch::Tensor> bwd_chain_wide(torch::Tensor probs,
                                           std::vector<torch::Tensor> hs,
                                           std::vector<torch::Tensor> w_ts,
                                           int64_t rows, int64_t waves,
-                                          int64_t loss) {
+                                          int64_t loss, double dz_scale) {
     const int64_t n = (int64_t)hs.size();
     const int64_t nw = (int64_t)w_ts.size();
     if (n < 1 || n > SS_BWD_CHAIN_MAX || (nw != n && nw != n - 1)) return {};
@@ -1055,7 +1097,7 @@ std::vector<torch::Tensor> bwd_chain_wide(torch::Tensor probs,
                            w_head_t.data_ptr(), out[0].data_ptr(), hp, wp, dp,
                            (int)n, dx_p, (int)M, (int)H, (int)C,
                            (float)(1.0 / global_batch), (int)rows, (int)waves,
-                           (int)loss, cur_stream()))
+                           (float)dz_scale, (int)loss, cur_stream()))
         return {};
     return out;
 }
@@ -1476,7 +1518,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "-> [dz_head, dz_l..., (dx)], or [] outside the contract",
           py::arg("probs"), py::arg("target"), py::arg("w_head_t"),
           py::arg("global_batch"), py::arg("hs"), py::arg("w_ts"),
-          py::arg("rows") = 0, py::arg("waves") = 0, py::arg("loss") = 0);
+          py::arg("rows") = 0, py::arg("waves") = 0, py::arg("loss") = 0,
+          py::arg("dz_scale") = 1.0);
+    m.def("fwd_chain_wide_dropout", &fwd_chain_wide_dropout,
+          "fwd_chain_wide with each layer's dropout mask in its epilogue -> "
+          "[h_l..., probs], or [] outside the contract",
+          py::arg("x"), py::arg("ws"), py::arg("bs"), py::arg("w_head"),
+          py::arg("b_head"), py::arg("key0"), py::arg("key1"),
+          py::arg("step"), py::arg("layers"), py::arg("thrs"),
+          py::arg("scales"), py::arg("drops"), py::arg("row_first"),
+          py::arg("row_stride"), py::arg("rows") = 0, py::arg("waves") = 0);
     m.def("head_metrics", &head_metrics,
           "metric totals of (probs, target) into a slotted accumulator",
           py::arg("probs"), py::arg("target"), py::arg("acc"),

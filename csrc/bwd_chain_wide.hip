@@ -6,6 +6,7 @@
 //   dh      = bf16(dz_head · W_head)
 //   per ReLU layer l, top to bottom (all H wide):
 //     dz_l  = !(h_l > 0) ? +0 : dh                           (stored)
+//             under dropout: !(h_l > 0) ? +0 : bf16(dh · dz_scale)
 //     dh    = bf16(dz_l · W_l)          while the layer's dgrad is in
 //                                       the chain; else the chain ends
 //   dx      = dh of the last layer      (stored, when that dgrad is in)
@@ -22,7 +23,10 @@
 //
 // What goes to memory is dz_l, the MASKED gradient, as 16-B
 // row-contiguous stores: every weight-gradient kernel downstream runs
-// without a mask.  There is no dropout scale and no W-through-LDS arm.
+// without a mask.  There is no W-through-LDS arm.  Layers that ran
+// inverted dropout take the SCALED instantiations (dz_scale != 1, one
+// value per launch): the stashed post-dropout h_l is the mask, and a kept
+// element is relu_bwd_scaled_kernel's, bf16(f32(dh) · dz_scale).
 //
 // Bits: dz_head and the head's dh come from the device code that
 // head_bwd_fused_kernel runs (head_dev.h: one MFMA per 16x16 fragment
@@ -64,12 +68,12 @@ bool ss_bwd_chain_wide(const void* probs, const void* target,
                        const void* Wt_head, void* dz_head,
                        const void* const* h, const void* const* wt,
                        void* const* dz, int nlayers, void* dx, int M, int H,
-                       int C, float inv_gb, int rows, int waves, int loss,
-                       hipStream_t st) {
+                       int C, float inv_gb, int rows, int waves,
+                       float dz_scale, int loss, hipStream_t st) {
     if (loss != 0 && loss != 1) return false;
     return (loss ? ss_bwd_chain_wide_mse : ss_bwd_chain_wide_xent)(
         probs, target, Wt_head, dz_head, h, wt, dz, nlayers, dx, M, H, C,
-        inv_gb, rows, waves, st);
+        inv_gb, rows, waves, dz_scale, st);
 }
 
 #if defined(__HIP_DEVICE_COMPILE__)

@@ -6,6 +6,17 @@
 // launcher) and BWD_WIDE_MSE (0 / 1).  With 1 the head step computes the
 // softmax-MSE dz, whose row sum every lane of the wave takes part in
 // (head_dev.h: head_mse_dz_elem); nothing else differs.
+//
+// SCALED: the layers ran inverted dropout, so a kept dz element is
+// bf16(dh · dz_scale) with dz_scale = 1/keep, one value for the launch
+// (the stashed post-dropout h already is the mask: h > 0 ⇔ z > 0 ∧ kept).
+// That is relu_bwd_scaled_kernel's value: the tile's bf16 dh, ONE f32
+// multiply, a second rounding.  The multiply has nothing to fuse with,
+// and the including files are built without packed f32 arithmetic, so it
+// stays one v_mul_f32 per element (bwd_chain_stage.hip's chain_unpaired
+// note is about a file built WITH packed f32).  SA is that float: an
+// EMPTY pack when not SCALED, so those instantiations keep their kernel
+// arguments and code.
 
 #include "chain_wide.h"
 
@@ -19,7 +30,7 @@ struct BwdWideLayers {
     void* dz[SS_BWD_CHAIN_MAX];        // masked gradient out
 };
 
-template <int HH, int R, int NW>
+template <int HH, int R, int NW, bool SCALED = false, class... SA>
 __global__ __launch_bounds__(NW * 64)
 void BWD_WIDE_KERNEL(
     const __bf16* __restrict__ probs,    // [M][C]
@@ -28,7 +39,8 @@ void BWD_WIDE_KERNEL(
     __bf16* __restrict__ dz_head,        // [M][C]
     const BwdWideLayers L, int nlayers,
     __bf16* __restrict__ dx,             // [M][H] or null
-    int M, int C, float inv_gb) {
+    int M, int C, float inv_gb, SA... dz_scale) {
+    static_assert(sizeof...(SA) == SCALED, "one dz_scale when SCALED");
     // the names CHAIN_LAYER_MMA_AHEAD, CHAIN_ACC_TO_TILE and
     // CHAIN_FOR_PIECES read
     constexpr int H = HH;
@@ -132,8 +144,11 @@ void BWD_WIDE_KERNEL(
         CHAIN_FOR_PIECES(i, r, col) {
             bf16x8 v = *(const bf16x8*)&tile[r][col];
 #pragma unroll
-            for (int e = 0; e < 8; ++e)
+            for (int e = 0; e < 8; ++e) {
                 if (!(bf2f(hm[i][e]) > 0.f)) v[e] = (__bf16)0.f;
+                else if constexpr (SCALED)
+                    v[e] = f2bf(bf2f(v[e]) * (dz_scale + ...));
+            }
             *(bf16x8*)&tile[r][col] = v;
             if (row0 + r < M)
                 *(gbf16x8*)&dzo[(long)(row0 + r) * H + col] = v;
@@ -170,12 +185,14 @@ void BWD_WIDE_KERNEL(
 // This loss's arm of ss_bwd_chain_wide (launchers.h), which selects it.
 // rows / waves: 0 = the shipped choice (docs/KERNELS.md, "Chain kernels,
 // wide"); any other pair must be one of with_chain_wide_arm's.
+// dz_scale: 1.f runs the unscaled instantiations; any other value the
+// scaled ones, built for every arm.
 bool BWD_WIDE_LAUNCHER(const void* probs, const void* target,
                        const void* Wt_head, void* dz_head,
                        const void* const* h, const void* const* wt,
                        void* const* dz, int nlayers, void* dx, int M, int H,
                        int C, float inv_gb, int rows, int waves,
-                       hipStream_t st) {
+                       float dz_scale, hipStream_t st) {
     if (M < 1 || M > INT32_MAX - 64 || (H != 128 && H != 512) || C < 1 ||
         C > 16 || nlayers < 1 || nlayers > SS_BWD_CHAIN_MAX)
         return false;
@@ -196,11 +213,18 @@ bool BWD_WIDE_LAUNCHER(const void* probs, const void* target,
     chain_wide_shipped(H, M, rows, waves);
     auto launch = [&](auto hh, auto r, auto nw) {
         constexpr int HH = hh.value, R = r.value, NW = nw.value;
-        hipLaunchKernelGGL((BWD_WIDE_KERNEL<HH, R, NW>),
-                           dim3(cdiv(M, R)), dim3(NW * 64), 0, st,
-                           (const __bf16*)probs, (const __bf16*)target,
-                           (const __bf16*)Wt_head, (__bf16*)dz_head, L,
-                           nlayers, (__bf16*)dx, M, C, inv_gb);
+        if (dz_scale != 1.f)
+            hipLaunchKernelGGL((BWD_WIDE_KERNEL<HH, R, NW, true, float>),
+                               dim3(cdiv(M, R)), dim3(NW * 64), 0, st,
+                               (const __bf16*)probs, (const __bf16*)target,
+                               (const __bf16*)Wt_head, (__bf16*)dz_head, L,
+                               nlayers, (__bf16*)dx, M, C, inv_gb, dz_scale);
+        else
+            hipLaunchKernelGGL((BWD_WIDE_KERNEL<HH, R, NW>),
+                               dim3(cdiv(M, R)), dim3(NW * 64), 0, st,
+                               (const __bf16*)probs, (const __bf16*)target,
+                               (const __bf16*)Wt_head, (__bf16*)dz_head, L,
+                               nlayers, (__bf16*)dx, M, C, inv_gb);
     };
     return H == 128 ? with_chain_wide_arm<128>(rows, waves, launch)
                     : with_chain_wide_arm<512>(rows, waves, launch);

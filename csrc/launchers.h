@@ -275,8 +275,8 @@ bool ss_fwd_chain_stage_drop(const void* x, const void* const* w,
 // ss_bwd_chain's pointer lists.  The first layer always streams x (any
 // K0 % 8 == 0, K0 == H included).  rows / waves: both 0 = the shipped
 // arm of (H, M), else one of the pairs built for H: (32, 4), (64, 4) at
-// 128; (32, 8), (64, 8), (64, 16) at 512.  No zeroing, no dropout scale,
-// no W-through-LDS arm.
+// 128; (32, 8), (64, 8), (64, 16) at 512.  No zeroing, no W-through-LDS
+// arm.  dz_scale as ss_bwd_chain's, built for every arm.
 // Host only: whether (rows, waves) selects an arm built for H (both 0
 // does, at H = 128 and 512), so that a caller can refuse before it
 // allocates.
@@ -290,20 +290,34 @@ bool ss_bwd_chain_wide(const void* probs, const void* target,
                        const void* Wt_head, void* dz_head,
                        const void* const* h, const void* const* wt,
                        void* const* dz, int nlayers, void* dx, int M, int H,
-                       int C, float inv_gb, int rows, int waves, int loss,
-                       hipStream_t stream);
+                       int C, float inv_gb, int rows, int waves,
+                       float dz_scale, int loss, hipStream_t stream);
 bool ss_bwd_chain_wide_xent(const void* probs, const void* target,
                             const void* Wt_head, void* dz_head,
                             const void* const* h, const void* const* wt,
                             void* const* dz, int nlayers, void* dx, int M,
                             int H, int C, float inv_gb, int rows, int waves,
+                            float dz_scale,
                             hipStream_t stream);  // bwd_chain_wide.hip
 bool ss_bwd_chain_wide_mse(const void* probs, const void* target,
                            const void* Wt_head, void* dz_head,
                            const void* const* h, const void* const* wt,
                            void* const* dz, int nlayers, void* dx, int M,
                            int H, int C, float inv_gb, int rows, int waves,
+                           float dz_scale,
                            hipStream_t stream);  // bwd_chain_wide_mse.hip
+
+// ---- fwd_chain_wide_drop.hip
+// ss_fwd_chain_wide under dropout, with fwd_chain_drop.hip's block and
+// epilogue: false as well when `on` names no layer or one at or past
+// nlayers, when a named layer's scale / threshold is none that a p in
+// [0, 1) gives, or when the last row's sample id reaches 2^32.
+bool ss_fwd_chain_wide_dropout(const void* x, const void* const* w,
+                               const void* const* b, void* const* h,
+                               int nlayers, const void* W_head,
+                               const void* b_head, void* probs, int M, int K0,
+                               int H, int C, int rows, int waves,
+                               const FwdChainDrop& drop, hipStream_t stream);
 
 // ---- fused_mlp.hip
 bool ss_fused_mlp_fwd(const void* x, const void* desc, int M, int in_dim,

@@ -9,7 +9,13 @@ against the per-layer launches they replace:
 
 Times are device-event time over back-to-back launches (launch gaps
 included), per call in µs; the arms alternate inside every round and the
-table gives the best, the median and the slowest round.  Needs a GPU."""
+table gives the best, the median and the slowest round.  Needs a GPU.
+
+  python scripts/microbench_chain_wide.py dropout
+              the same shapes with p = 0.2 on every ReLU layer: the
+              per-layer path against fwd_chain_wide_dropout and
+              bwd_chain_wide(dz_scale), both kernels and the training
+              step (profiles/r24_chain_wide_dropout.md)"""
 import statistics
 import sys
 
@@ -52,6 +58,85 @@ def bench(arms):
 def rnd(*shape, scale=1.0):
     return (torch.randn(*shape, generator=g) * scale).to(dev).bfloat16()
 
+
+def dropout_section():
+    """`dropout`: p = 0.2 on every ReLU layer, per width and batch, the
+    shipped arm.  Forward: 3 x gemm_nt_dropout + head_fwd_fused against
+    fwd_chain_wide_dropout, and fwd_chain_wide to price the mask.
+    Backward: head_bwd_fused + 3 x relu_bwd(scale) + 2 x gemm_nt against
+    bwd_chain_wide(dz_scale), and the unscaled launch.  Step: zero_grad,
+    forward, backward, SGD of one model, F.set_chain_wide_dropout off
+    against on (the wide chains themselves switched on for both)."""
+    from shallowspeed_amd.models import MLP, SGD
+
+    p, seed, layers = 0.2, 0x1234567887654321, (0, 1, 2)
+    thr, scale = F.dropout_params(p)
+    k0, k1 = seed & 0xFFFFFFFF, seed >> 32
+    F.set_chain_wide(True)
+    for H in F.CHAIN_WIDE_WIDTHS:
+        for M in (1024, 16384):
+            x = rnd(M, IN0)
+            dims = [IN0] + [H] * N
+            ws = [rnd(H, dims[l], scale=dims[l] ** -0.5) for l in range(N)]
+            bs = [rnd(H, scale=0.1) for _ in range(N)]
+            w_head, b_head = rnd(C, H, scale=H ** -0.5), rnd(C, scale=0.1)
+            w_head_t = w_head.t().contiguous()
+            w_ts = [w.t().contiguous() for w in ws[:0:-1]]  # top first
+            target = torch.eye(C)[torch.arange(M) % C].to(dev).bfloat16()
+            key = (seed, 7, layers, (p,) * N, 0, 1)
+            hs, probs = F.fwd_chain_wide_dropout(x, ws, bs, w_head, b_head,
+                                                 *key)
+            hs_top = hs[::-1]
+
+            def fwd_layers():
+                h = x
+                for l, w, b in zip(layers, ws, bs):
+                    h = e.gemm_nt_dropout(h, w, b, k0, k1, 7, l, 0, 1, thr,
+                                          scale, True)
+                return e.head_fwd_fused(h, w_head, b_head)
+
+            def bwd_layers():
+                _, dh = e.head_bwd_fused(probs, target, hs_top[0], w_head_t,
+                                         float(GB), empty, empty)
+                for l in range(N):
+                    dz = F.relu_bwd(dh, hs_top[l], scale=scale)
+                    if l < len(w_ts):
+                        dh = e.gemm_nt(dz, w_ts[l], empty, empty, False)
+
+            print(f"dropout p={p} H={H} M={M} in={IN0} layers={N} C={C}")
+            bench({
+                "forward per layer (dropout)": fwd_layers,
+                "fwd_chain_wide_dropout": lambda: F.fwd_chain_wide_dropout(
+                    x, ws, bs, w_head, b_head, *key),
+                "fwd_chain_wide (no mask)": lambda: F.fwd_chain_wide(
+                    x, ws, bs, w_head, b_head),
+                "backward per layer (scaled)": bwd_layers,
+                "bwd_chain_wide dz_scale": lambda: F.bwd_chain_wide(
+                    probs, target, w_head_t, GB, hs_top, w_ts,
+                    dz_scale=scale),
+                "bwd_chain_wide (no scale)": lambda: F.bwd_chain_wide(
+                    probs, target, w_head_t, GB, hs_top, w_ts),
+            })
+            model = MLP([IN0] + [H] * N + [C], 0, 1, M, dropout=p,
+                        dropout_seed=seed).materialize_device(dev)
+            opt = SGD(model.parameters(), lr=0.01)
+
+            def step(on):
+                F.set_chain_wide_dropout(on)
+                model.zero_grad()
+                model.forward(x, 0)
+                model.backward(target, 0)
+                opt.step()
+                model.dropout_step += 1
+
+            bench({"step, SS_CHAIN_WIDE_DROPOUT off": lambda: step(False),
+                   "step, SS_CHAIN_WIDE_DROPOUT on": lambda: step(True)})
+    F.set_chain_wide_dropout(False)
+
+
+if sys.argv[1:] == ["dropout"]:
+    dropout_section()
+    sys.exit(0)
 
 for H in F.CHAIN_WIDE_WIDTHS:
     for M in (1024, 16384):

@@ -742,8 +742,11 @@ class Sequential(Module):
         "relu") layers with out_dims == H right under the fused head, at
         most eight.  A layer is in the chain when in_dims == H, or when
         it ends the run and in_dims % 8 == 0 (the kernel streams the
-        input of its first layer).  None with dropout or an fp8 forward
-        on a layer it would take.  Consulted only where
+        input of its first layer).  None with an fp8 forward on a layer
+        it would take, and with dropout on one unless
+        F.chain_wide_dropout_enabled(): then the plan is the plain
+        model's, for F.fwd_chain_wide_dropout in training mode and
+        F.fwd_chain_wide in eval mode.  Consulted only where
         _fwd_chain_plan() is None; width 256 is that plan's.  rows: the
         micro-batch rows, where the caller knows them."""
         width = self._wide_head_width(rows)
@@ -755,7 +758,8 @@ class Sequential(Module):
             streamed = layer.in_dims != width
             if streamed and (layer.in_dims < 8 or layer.in_dims % 8 != 0):
                 break
-            if layer.dropout > 0.0 or layer.fp8_fwd:
+            if layer.fp8_fwd or layer.dropout > 0.0 \
+                    and not F.chain_wide_dropout_enabled():
                 return None
             plan.append(i)
             if streamed:
@@ -768,21 +772,27 @@ class Sequential(Module):
         is in the chain when in_dims == H and its dx is needed; the
         chain ends with the first layer whose dgrad is not (that layer
         still gets its dz from the kernel).  None with dropout on a
-        planned layer (the kernel has no dz scale).  Consulted only
-        where _bwd_chain_plan() is None."""
+        planned layer unless F.chain_wide_dropout_enabled().  Consulted
+        only where _bwd_chain_plan() is None."""
         width = self._wide_head_width(mubatch_rows)
         if width is None or mubatch_rows < 1:
             return None
         plan = []
         for i in self._chain_run(width=width):
             layer = self.layers[i]
-            if layer.dropout > 0.0:
+            if layer.dropout > 0.0 and not F.chain_wide_dropout_enabled():
                 return None
             need_dx = not (i == 0 and self._skip_input_grad)
             in_chain = need_dx and layer.in_dims == width
             plan.append((i, in_chain))
             if not in_chain:
                 break
+        # one dz scale per launch: the chain only when every planned
+        # layer has the same drop probability (all 0: today's kernel);
+        # a mix takes the per-layer path
+        if self._has_dropout and \
+                len({self.layers[i].dz_scale() for i, _ in plan}) > 1:
+            return None
         return plan or None
 
     def _forward_chain(self, plan, lin, head, x, mubatch_id, launch=None,
@@ -795,9 +805,10 @@ class Sequential(Module):
         takes a deferred zero_grad along; returns the top layer's
         output.  launch (a wide plan): F.fwd_chain_wide in place of
         F.fwd_chain, which takes no deferred zero_grad along either.
-        drop (a _fwd_drop_plan): where a planned layer drops out in this
-        forward (training mode), F.fwd_chain_dropout /
-        F.fwd_chain_stage_dropout with the layers' own mask keys, so the
+        drop (a _fwd_drop_plan, or a wide plan of a model with dropout):
+        where a planned layer drops out in this forward (training mode),
+        F.fwd_chain_dropout / F.fwd_chain_stage_dropout /
+        F.fwd_chain_wide_dropout with the layers' own mask keys, so the
         stashed y are the post-dropout outputs Linear._forward_dropout
         leaves; else the plain launch."""
         chain = [self.layers[i] for i in plan]
@@ -831,7 +842,8 @@ class Sequential(Module):
                 [l.bias.compute() for l in chain],
                 lin.weight.compute(), lin.bias.compute())
         if launch:
-            res = launch(*args)
+            res = F.fwd_chain_wide_dropout(*args, *dargs) if dargs \
+                else launch(*args)
         elif dargs:
             res = F.fwd_chain_dropout(*args, *dargs, zero=zero)
         else:
@@ -861,6 +873,7 @@ class Sequential(Module):
             if plan is None and pair:
                 plan = self._fwd_wide_plan(inputs.shape[0])
                 wide = F.fwd_chain_wide if plan else None
+                drop = plan is not None and self._has_dropout
             if plan is None:
                 plan = self._fwd_drop_plan()
                 drop = plan is not None
@@ -1018,8 +1031,8 @@ class Sequential(Module):
         lin = head = None (a stage plan): `target` is the gradient the
         stage received, and the launch is ONE F.bwd_chain_stage on it;
         the wgrads follow in the same way.  launch (a wide plan):
-        F.bwd_chain_wide in place of F.bwd_chain; everything after the
-        launch is the same."""
+        F.bwd_chain_wide in place of F.bwd_chain, with the same dz_scale;
+        everything after the launch is the same."""
         chain = [self.layers[i] for i, _ in plan]
         hs = [l._cache.get(("y", mubatch_id)) for l in chain]
         if lin is None:
@@ -1047,9 +1060,8 @@ class Sequential(Module):
                     for l, (_, dg) in zip(chain, plan) if dg]
             args = (s, target, lin.weight.compute_t(),
                     head.global_batch_size, hs, w_ts)
-            res = launch(*args, loss=head.kind) if launch else \
-                F.bwd_chain(*args, dz_scale=chain[0].dz_scale(),
-                            loss=head.kind)
+            res = (launch or F.bwd_chain)(
+                *args, dz_scale=chain[0].dz_scale(), loss=head.kind)
             if res is None:
                 return False, None
             dz_head, dzs, dx = res

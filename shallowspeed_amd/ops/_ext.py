@@ -94,6 +94,7 @@ def build_ext(verbose=True):
         os.path.join(src_dir, "fused_mlp_wide.hip"),
         os.path.join(src_dir, "fused_mlp_taper.hip"),
         os.path.join(src_dir, "fwd_chain_wide.hip"),
+        os.path.join(src_dir, "fwd_chain_wide_drop.hip"),
         os.path.join(src_dir, "bwd_chain_wide.hip"),
         os.path.join(src_dir, "bwd_chain_wide_mse.hip"),
     ]

@@ -301,6 +301,33 @@ def chain_wide_planned(width, rows=None) -> bool:
         rows is None or rows >= CHAIN_WIDE_MIN_ROWS[width])
 
 
+_CHAIN_WIDE_DROPOUT = None
+
+
+def set_chain_wide_dropout(flag: bool):
+    """Let a model with dropout on its 128- or 512-wide ReLU layers take
+    the wide chains too (Sequential._fwd_wide_plan / _bwd_wide_plan): in
+    training mode fwd_chain_wide_dropout, the mask in each layer's
+    epilogue, and bwd_chain_wide with the layers' dz_scale; in eval mode,
+    where the forward is the plain one, fwd_chain_wide.  Every h_l,
+    probs, dz and dx keeps its bits.  Planning still follows
+    chain_wide_planned, whose batch thresholds were measured WITHOUT
+    dropout.  Default OFF; SS_CHAIN_WIDE_DROPOUT=1 (read once) turns it
+    on (profiles/r24_chain_wide_dropout.md)."""
+    global _CHAIN_WIDE_DROPOUT
+    _CHAIN_WIDE_DROPOUT = bool(flag)
+
+
+def chain_wide_dropout_enabled() -> bool:
+    global _CHAIN_WIDE_DROPOUT
+    if _CHAIN_WIDE_DROPOUT is None:
+        import os
+
+        _CHAIN_WIDE_DROPOUT = \
+            os.environ.get("SS_CHAIN_WIDE_DROPOUT", "0") == "1"
+    return _CHAIN_WIDE_DROPOUT
+
+
 _FWD_CHAIN_L1 = None
 
 
@@ -1025,22 +1052,57 @@ def fwd_chain_wide(x, ws, bs, w_head, b_head, rows=0, waves=0):
     return out[:-1], out[-1]
 
 
+def fwd_chain_wide_dropout(x, ws, bs, w_head, b_head, seed, step, layers, ps,
+                           row_first, row_stride, rows=0, waves=0):
+    """fwd_chain_wide for a training forward under dropout, still one
+    kernel (GPU only, csrc/fwd_chain_wide_drop.hip).
+
+      h_l = dropout_l(relu(h_{l-1} @ W_l^T + b_l))
+      probs = softmax(h @ W_head^T + b)
+
+    layers / ps / seed / step / row_first / row_stride as
+    fwd_chain_dropout: the mask is drawn ahead of each layer's K loop and
+    applied in its epilogue, and the dropped-out tile is the next layer's
+    input.  A layer with p = 0 runs the plain epilogue.
+
+    Returns ([h_l, ...], probs), each bit-identical to
+    linear_fwd_dropout (linear_fwd(relu) where p = 0) -> ... ->
+    head_fwd_fused, or None, with nothing launched, outside the kernel's
+    contract: fwd_chain_wide's, plus at least one p > 0 and every sample
+    id below 2^32.  A p outside [0, 1) raises, as dropout_params does."""
+    if not _is_gpu(x):
+        return None
+    drop = _chain_drop_args(x, seed, step, layers, ps, row_first, row_stride)
+    if drop is None:
+        return None
+    out = _ext_for(x).fwd_chain_wide_dropout(
+        x, list(ws), list(bs), w_head, b_head, *drop, int(rows), int(waves))
+    if not out:
+        return None
+    return out[:-1], out[-1]
+
+
 def bwd_chain_wide(probs, target, w_head_t, global_batch, hs, w_ts, rows=0,
-                   waves=0, loss="xent"):
+                   waves=0, loss="xent", dz_scale=1.0):
     """bwd_chain at hidden width H = 128 or 512 (GPU only,
     csrc/bwd_chain_wide.hip); H is w_head_t's row count.  hs / w_ts as
-    bwd_chain, loss as there.  No dropout scale.
+    bwd_chain, loss as there.
 
     Returns (dz_head, [dz_l, ...], dx or None), each bit-identical to
     head_bwd_fused -> relu_bwd -> linear_dgrad -> ..., or None, with
     nothing launched, outside the kernel's contract (see
-    fwd_chain_wide)."""
+    fwd_chain_wide).
+
+    dz_scale != 1 (layers under inverted dropout, all with one p; hs are
+    their post-dropout outputs): every kept dz_l element is
+    bf16(dh · dz_scale), bit-identical to relu_bwd(dh, h_l,
+    scale=dz_scale).  One scale per launch, built for every arm."""
     if not _is_gpu(probs):
         return None
     out = _ext_for(probs).bwd_chain_wide(probs, target, w_head_t,
                                          float(global_batch), list(hs),
                                          list(w_ts), int(rows), int(waves),
-                                         _HEAD_LOSS[loss])
+                                         _HEAD_LOSS[loss], float(dz_scale))
     if not out:
         return None
     n = len(hs)

@@ -188,6 +188,16 @@ def main():
 
         _F.set_fwd_chain_dropout(True)
 
+    if args.dropout > 0 and "SS_CHAIN_WIDE_DROPOUT" not in os.environ:
+        # the wide chains (H = 128, 512) under dropout, where the wide
+        # chains are planned at all (F.chain_wide_planned: 512 wide from
+        # 16384 rows): there the step measured 225 against 292 us, a
+        # spread of 1 us (profiles/r24_chain_wide_dropout.md);
+        # SS_CHAIN_WIDE_DROPOUT=0 keeps the per-layer step
+        from shallowspeed_amd.ops import functional as _F
+
+        _F.set_chain_wide_dropout(True)
+
     if args.loss == "mse" and "SS_HEAD_MSE_FUSED" not in os.environ:
         # the fused head and the chain kernels under the softmax-MSE head:
         # measured ahead of the per-layer step by far more than five times
