@@ -1102,6 +1102,108 @@ std::vector<torch::Tensor> bwd_chain_wide(torch::Tensor probs,
     return out;
 }
 
+// Stage arm of the wide forward chain (fwd_chain_wide_stage.hip), for a
+// pipeline stage with no head: H = 128 or 512 read from ws[0], start as
+// ss_fwd_chain_wide_stage's.  Returns [h_0, ..., h_{n-1}], or an EMPTY
+// list with nothing allocated or launched outside the kernel's contract.
+// drop != null: the arm under dropout, with fwd_chain_wide_any's refusals.
+static std::vector<torch::Tensor> fwd_chain_wide_stage_any(
+    const torch::Tensor& x, const std::vector<torch::Tensor>& ws,
+    const std::vector<torch::Tensor>& bs, int64_t rows, int64_t waves,
+    int64_t start, const FwdChainDrop* drop = nullptr) {
+    const int64_t n = (int64_t)ws.size();
+    if (n < 1 || n > SS_FWD_CHAIN_MAX || (int64_t)bs.size() != n) return {};
+    if (drop && (drop->on == 0 || (drop->on >> n) != 0 || x.dim() != 2 ||
+                 (int64_t)drop->row_first +
+                         (x.size(0) - 1) * (int64_t)drop->row_stride >
+                     (int64_t)UINT_MAX))
+        return {};
+    if (!plain(x, 2) || !plain(ws[0], 2)) return {};
+    const int64_t M = x.size(0), K0 = x.size(1), H = ws[0].size(0);
+    if (M < 1 || M > INT_MAX / 1024 || K0 < 8 || K0 % 8 != 0 || start < 0 ||
+        start > 2 || (start == 2 && K0 != H) ||
+        !ss_chain_wide_arm_built((int)H, (int)rows, (int)waves))
+        return {};
+    const void* wp[SS_FWD_CHAIN_MAX] = {};
+    const void* bp[SS_FWD_CHAIN_MAX] = {};
+    void* hp[SS_FWD_CHAIN_MAX] = {};
+    for (int64_t l = 0; l < n; ++l) {
+        if (!plain(ws[l], 2) || !plain(bs[l], 1) || ws[l].size(0) != H ||
+            ws[l].size(1) != (l == 0 ? K0 : H) || bs[l].numel() != H)
+            return {};
+        wp[l] = ws[l].data_ptr();
+        bp[l] = bs[l].data_ptr();
+    }
+    std::vector<torch::Tensor> out;
+    for (int64_t l = 0; l < n; ++l) {
+        out.push_back(torch::empty({M, H}, x.options()));
+        hp[l] = out.back().data_ptr();
+    }
+    if (!(drop ? ss_fwd_chain_wide_stage_dropout(
+                     x.data_ptr(), wp, bp, hp, (int)n, (int)M, (int)K0,
+                     (int)H, (int)rows, (int)waves, (int)start, *drop,
+                     cur_stream())
+               : ss_fwd_chain_wide_stage(x.data_ptr(), wp, bp, hp, (int)n,
+                                         (int)M, (int)K0, (int)H, (int)rows,
+                                         (int)waves, (int)start,
+                                         cur_stream())))
+        return {};
+    return out;
+}
+
+std::vector<torch::Tensor> fwd_chain_wide_stage(torch::Tensor x,
+                                                std::vector<torch::Tensor> ws,
+                                                std::vector<torch::Tensor> bs,
+                                                int64_t rows, int64_t waves,
+                                                int64_t start) {
+    return fwd_chain_wide_stage_any(x, ws, bs, rows, waves, start);
+}
+
+// Its arm under dropout (fwd_chain_wide_stage_drop.hip): the block as
+// fwd_chain_wide_dropout's; [h_0, ..., h_{n-1}] or EMPTY.
+std::vector<torch::Tensor> fwd_chain_wide_stage_dropout(
+    torch::Tensor x, std::vector<torch::Tensor> ws,
+    std::vector<torch::Tensor> bs, int64_t key0, int64_t key1, int64_t step,
+    std::vector<int64_t> layers, std::vector<int64_t> thrs,
+    std::vector<double> scales, std::vector<bool> drops, int64_t row_first,
+    int64_t row_stride, int64_t rows, int64_t waves, int64_t start) {
+    FwdChainDrop d;
+    if (!fwd_chain_drop_block(d, (int64_t)ws.size(), key0, key1, step, layers,
+                              thrs, scales, drops, row_first, row_stride))
+        return {};
+    return fwd_chain_wide_stage_any(x, ws, bs, rows, waves, start, &d);
+}
+
+// Stage arm of the wide backward chain (bwd_chain_wide_stage.hip): the
+// chain starts from dout [M][H], H = 128 or 512.  hs / w_ts as bwd_chain.
+// Returns [dz_0, ..., dz_{n-1}(, dx)], or an EMPTY list with nothing
+// allocated or launched.  dz_scale as bwd_chain_wide's.
+std::vector<torch::Tensor> bwd_chain_wide_stage(torch::Tensor dout,
+                                                std::vector<torch::Tensor> hs,
+                                                std::vector<torch::Tensor> w_ts,
+                                                int64_t rows, int64_t waves,
+                                                double dz_scale) {
+    const int64_t n = (int64_t)hs.size();
+    const int64_t nw = (int64_t)w_ts.size();
+    if (n < 1 || n > SS_BWD_CHAIN_MAX || (nw != n && nw != n - 1)) return {};
+    if (!plain(dout, 2)) return {};
+    const int64_t M = dout.size(0), H = dout.size(1);
+    if (M < 1 || M > INT_MAX / 1024 ||
+        !ss_chain_wide_arm_built((int)H, (int)rows, (int)waves))
+        return {};
+    const void* hp[SS_BWD_CHAIN_MAX] = {};
+    const void* wp[SS_BWD_CHAIN_MAX] = {};
+    void* dp[SS_BWD_CHAIN_MAX] = {};
+    if (!bwd_chain_operands(hs, w_ts, M, H, hp, wp)) return {};
+    std::vector<torch::Tensor> out;
+    void* dx_p = bwd_chain_outputs(hs, nw == n, out, dp);
+    if (!ss_bwd_chain_wide_stage(dout.data_ptr(), hp, wp, dp, (int)n, dx_p,
+                                 (int)M, (int)H, (int)rows, (int)waves,
+                                 (float)dz_scale, cur_stream()))
+        return {};
+    return out;
+}
+
 // Adds the metric totals of (probs, target) into acc: loss_sum (kind
 // "xent" or "mse"), argmax matches, rows, non-finite rows.
 void head_metrics(torch::Tensor probs, torch::Tensor target,
@@ -1528,6 +1630,26 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           py::arg("step"), py::arg("layers"), py::arg("thrs"),
           py::arg("scales"), py::arg("drops"), py::arg("row_first"),
           py::arg("row_stride"), py::arg("rows") = 0, py::arg("waves") = 0);
+    m.def("fwd_chain_wide_stage", &fwd_chain_wide_stage,
+          "H-wide ReLU layers (H = 128 or 512) of a headless pipeline stage "
+          "in one launch -> [h_l...], or [] outside the contract",
+          py::arg("x"), py::arg("ws"), py::arg("bs"), py::arg("rows") = 0,
+          py::arg("waves") = 0, py::arg("start") = 0);
+    m.def("fwd_chain_wide_stage_dropout", &fwd_chain_wide_stage_dropout,
+          "fwd_chain_wide_stage with each layer's dropout mask in its "
+          "epilogue -> [h_l...], or [] outside the contract",
+          py::arg("x"), py::arg("ws"), py::arg("bs"), py::arg("key0"),
+          py::arg("key1"), py::arg("step"), py::arg("layers"),
+          py::arg("thrs"), py::arg("scales"), py::arg("drops"),
+          py::arg("row_first"), py::arg("row_stride"), py::arg("rows") = 0,
+          py::arg("waves") = 0, py::arg("start") = 0);
+    m.def("bwd_chain_wide_stage", &bwd_chain_wide_stage,
+          "H-wide ReLU dgrads (H = 128 or 512) of a headless pipeline stage "
+          "from dout in one launch -> [dz_l..., (dx)], or [] outside the "
+          "contract",
+          py::arg("dout"), py::arg("hs"), py::arg("w_ts"),
+          py::arg("rows") = 0, py::arg("waves") = 0,
+          py::arg("dz_scale") = 1.0);
     m.def("head_metrics", &head_metrics,
           "metric totals of (probs, target) into a slotted accumulator",
           py::arg("probs"), py::arg("target"), py::arg("acc"),

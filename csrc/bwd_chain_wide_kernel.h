@@ -7,6 +7,15 @@
 // softmax-MSE dz, whose row sum every lane of the wave takes part in
 // (head_dev.h: head_mse_dz_elem); nothing else differs.
 //
+// BWD_WIDE_HEAD (optional, default 1) 0 is the stage arm
+// (bwd_chain_wide_stage.hip), for a pipeline stage with no classifier
+// head: the chain is entered from dout [M][H], the received gradient of
+// the top layer's output, in memory.  No head step, so no W_head^T and no
+// dz_head in LDS: a thread takes its pieces of dout and of the top layer's
+// mask source into registers, masks them there and writes dz_0 once to the
+// tile and once to memory.  From the first K loop on the text is the
+// headed kernel's.
+//
 // SCALED: the layers ran inverted dropout, so a kept dz element is
 // bf16(dh · dz_scale) with dz_scale = 1/keep, one value for the launch
 // (the stashed post-dropout h already is the mask: h > 0 ⇔ z > 0 ∧ kept).
@@ -19,6 +28,10 @@
 // arguments and code.
 
 #include "chain_wide.h"
+
+#ifndef BWD_WIDE_HEAD
+#define BWD_WIDE_HEAD 1
+#endif
 
 namespace {
 
@@ -33,13 +46,21 @@ struct BwdWideLayers {
 template <int HH, int R, int NW, bool SCALED = false, class... SA>
 __global__ __launch_bounds__(NW * 64)
 void BWD_WIDE_KERNEL(
+#if BWD_WIDE_HEAD
     const __bf16* __restrict__ probs,    // [M][C]
     const __bf16* __restrict__ target,   // [M][C]
     const __bf16* __restrict__ Wt_head,  // [H][C]
     __bf16* __restrict__ dz_head,        // [M][C]
+#else
+    const __bf16* __restrict__ dout,     // [M][H]: dh of the top layer
+#endif
     const BwdWideLayers L, int nlayers,
     __bf16* __restrict__ dx,             // [M][H] or null
+#if BWD_WIDE_HEAD
     int M, int C, float inv_gb, SA... dz_scale) {
+#else
+    int M, SA... dz_scale) {
+#endif
     static_assert(sizeof...(SA) == SCALED, "one dz_scale when SCALED");
     // the names CHAIN_LAYER_MMA_AHEAD, CHAIN_ACC_TO_TILE and
     // CHAIN_FOR_PIECES read
@@ -52,10 +73,14 @@ void BWD_WIDE_KERNEL(
     constexpr int WN = H / NW;        // columns per wave
     constexpr int FN = WN / 16;
     constexpr int NSTEP = H / 32;     // K-steps of a layer
+#if BWD_WIDE_HEAD
     constexpr int HC = H < 256 ? H : 256;  // W_head^T rows per staged chunk
+#endif
     static_assert(WN % 16 == 0 && FN >= 1 && R % 16 == 0, "fragment split");
     static_assert(R * PPR % NT == 0 && NP >= 1, "piece mapping");
+#if BWD_WIDE_HEAD
     static_assert(NT >= HC && H % HC == 0, "one thread per W_head^T row");
+#endif
     static_assert(NSTEP > CHAIN_B_AHEAD, "K loop");
     // every built arm keeps B three K-steps ahead: accumulators + the ring
     // of four B sets + the A fragments + the mask source that is in
@@ -65,8 +90,10 @@ void BWD_WIDE_KERNEL(
                   "register budget of CHAIN_LAYER_MMA_AHEAD");
 
     __shared__ __attribute__((aligned(16))) ushort tile[R][LDT];
+#if BWD_WIDE_HEAD
     __shared__ __attribute__((aligned(16))) ushort wts[HC][16];
     __shared__ __attribute__((aligned(16))) ushort dzs[R][16];
+#endif
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -88,6 +115,7 @@ void BWD_WIDE_KERNEL(
     };
     load_mask(0);
 
+#if BWD_WIDE_HEAD
     // ---- head: dz_head of the tile, stored and kept as the MFMA A
     // operand (class index = k slot, k >= C zero)
     for (int e = tid; e < R * 16; e += NT) {
@@ -134,6 +162,33 @@ void BWD_WIDE_KERNEL(
         }
     }
     __syncthreads();
+#else
+    // ---- entry: dz_0 from dout and h_0, both in registers (rows past M
+    // as zeros, never stored).  One LDS write per piece, no LDS read, and
+    // no barrier ahead of it: a thread touches only its own pieces.  The
+    // rule and the scaled product are the mask pass's below.
+    {
+        gbf16* const dzo = (gbf16*)L.dz[0];
+        bf16x8 dv[NP];
+        CHAIN_FOR_PIECES(i, r, col) {
+            dv[i] = zero8();
+            if (row0 + r < M)
+                dv[i] = *(const bf16x8*)&dout[(long)(row0 + r) * H + col];
+        }
+        CHAIN_FOR_PIECES(i, r, col) {
+            bf16x8 v = dv[i];
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                if (!(bf2f(hm[i][e]) > 0.f)) v[e] = (__bf16)0.f;
+                else if constexpr (SCALED)
+                    v[e] = f2bf(bf2f(v[e]) * (dz_scale + ...));
+            }
+            *(bf16x8*)&tile[r][col] = v;
+            if (row0 + r < M)
+                *(gbf16x8*)&dzo[(long)(row0 + r) * H + col] = v;
+        }
+    }
+#endif
 
     // ---- the ReLU layers: the tile holds dh of layer l
     for (int l = 0; l < nlayers; ++l) {
@@ -141,6 +196,9 @@ void BWD_WIDE_KERNEL(
         // row-contiguous stores (a thread touches only its own pieces,
         // so no barrier inside the pass)
         gbf16* const dzo = (gbf16*)L.dz[l];
+#if !BWD_WIDE_HEAD
+        if (l > 0)  // the tile already holds dz_0
+#endif
         CHAIN_FOR_PIECES(i, r, col) {
             bf16x8 v = *(const bf16x8*)&tile[r][col];
 #pragma unroll
@@ -187,6 +245,7 @@ void BWD_WIDE_KERNEL(
 // wide"); any other pair must be one of with_chain_wide_arm's.
 // dz_scale: 1.f runs the unscaled instantiations; any other value the
 // scaled ones, built for every arm.
+#if BWD_WIDE_HEAD
 bool BWD_WIDE_LAUNCHER(const void* probs, const void* target,
                        const void* Wt_head, void* dz_head,
                        const void* const* h, const void* const* wt,
@@ -199,6 +258,15 @@ bool BWD_WIDE_LAUNCHER(const void* probs, const void* target,
     if (!aligned16(probs) || !aligned16(target) || !aligned16(Wt_head) ||
         !aligned16(dz_head))
         return false;
+#else
+bool BWD_WIDE_LAUNCHER(const void* dout, const void* const* h,
+                       const void* const* wt, void* const* dz, int nlayers,
+                       void* dx, int M, int H, int rows, int waves,
+                       float dz_scale, hipStream_t st) {
+    if (M < 1 || M > INT32_MAX - 64 || (H != 128 && H != 512) ||
+        nlayers < 1 || nlayers > SS_BWD_CHAIN_MAX || !aligned16(dout))
+        return false;
+#endif
     BwdWideLayers L = {};
     for (int l = 0; l < nlayers; ++l) {
         const bool last = l + 1 == nlayers;
@@ -213,6 +281,7 @@ bool BWD_WIDE_LAUNCHER(const void* probs, const void* target,
     chain_wide_shipped(H, M, rows, waves);
     auto launch = [&](auto hh, auto r, auto nw) {
         constexpr int HH = hh.value, R = r.value, NW = nw.value;
+#if BWD_WIDE_HEAD
         if (dz_scale != 1.f)
             hipLaunchKernelGGL((BWD_WIDE_KERNEL<HH, R, NW, true, float>),
                                dim3(cdiv(M, R)), dim3(NW * 64), 0, st,
@@ -225,6 +294,18 @@ bool BWD_WIDE_LAUNCHER(const void* probs, const void* target,
                                (const __bf16*)probs, (const __bf16*)target,
                                (const __bf16*)Wt_head, (__bf16*)dz_head, L,
                                nlayers, (__bf16*)dx, M, C, inv_gb);
+#else
+        if (dz_scale != 1.f)
+            hipLaunchKernelGGL((BWD_WIDE_KERNEL<HH, R, NW, true, float>),
+                               dim3(cdiv(M, R)), dim3(NW * 64), 0, st,
+                               (const __bf16*)dout, L, nlayers, (__bf16*)dx,
+                               M, dz_scale);
+        else
+            hipLaunchKernelGGL((BWD_WIDE_KERNEL<HH, R, NW>),
+                               dim3(cdiv(M, R)), dim3(NW * 64), 0, st,
+                               (const __bf16*)dout, L, nlayers, (__bf16*)dx,
+                               M);
+#endif
     };
     return H == 128 ? with_chain_wide_arm<128>(rows, waves, launch)
                     : with_chain_wide_arm<512>(rows, waves, launch);

@@ -12,6 +12,12 @@
 //                        loop (shipped, as at width 256)
 //                     1: in the epilogue (for an arm that cannot hold the
 //                        bits through its K loop)
+//   FWD_WIDE_HEAD     (optional, default 1) 0: the stage arm
+//                     (fwd_chain_wide_stage.hip, .._stage_drop.hip), for a
+//                     pipeline stage with no classifier head: no W_head /
+//                     b_head / probs / C, the kernel ends with the h_top
+//                     store, and layer 0 has a second start, from a
+//                     stored H-wide activation (`tile0`, below)
 //
 // The arms share text through the preprocessor and not through a
 // function template for fwd_chain_kernel.h's reason: this way the plain
@@ -23,6 +29,9 @@
 
 #ifndef FWD_WIDE_DROP
 #define FWD_WIDE_DROP 0
+#endif
+#ifndef FWD_WIDE_HEAD
+#define FWD_WIDE_HEAD 1
 #endif
 #if FWD_WIDE_DROP
 #include "dropout_dev.h"
@@ -46,10 +55,16 @@ void FWD_WIDE_KERNEL(
 #if FWD_WIDE_DROP
     const FwdChainDrop D,
 #endif
+#if FWD_WIDE_HEAD
     const __bf16* __restrict__ W_head,  // [C][H]
     const __bf16* __restrict__ b_head,  // [C]
     __bf16* __restrict__ probs,         // [M][C]
     int M, int K0, int C) {
+#else
+    // tile0 (block-uniform, K0 == H only): x goes straight into the tile
+    // and layer 0 runs the in-place K loop of the later layers
+    int M, int K0, int tile0) {
+#endif
     // the names CHAIN_LAYER_MMA_AHEAD, CHAIN_ACC_TO_TILE and
     // CHAIN_FOR_PIECES read
     constexpr int H = HH;
@@ -65,7 +80,9 @@ void FWD_WIDE_KERNEL(
     constexpr int NKB = FWD_WIDE_DROP ? (FM * FN + 7) / 8 : 0;
     static_assert(WN % 16 == 0 && FN >= 1 && R % 16 == 0, "fragment split");
     static_assert(R * PPR % NT == 0 && NP >= 1, "piece mapping");
+#if FWD_WIDE_HEAD
     static_assert(FM <= NW, "one head fragment per wave");
+#endif
     static_assert(NSTEP > CHAIN_B_AHEAD, "K loop");
     // every built arm keeps B three K-steps ahead: accumulators + the ring
     // of four B sets + the A fragments (+ the keep bits that stay live
@@ -166,6 +183,24 @@ void FWD_WIDE_KERNEL(
         }
     };
 
+#if FWD_WIDE_HEAD
+    constexpr int l0 = 1;
+#else
+    // ---- a middle stage: x is a stored H-wide activation and IS the
+    // tile of layer 0, rows past M as zeros.  No x stage and no chunk
+    // barriers: one barrier, then the loop below from l = 0, B three
+    // K-steps ahead.  Same K order as the streamed start, so same bits.
+    const int l0 = tile0 ? 0 : 1;
+    if (tile0) {
+        CHAIN_FOR_PIECES(i, r, col) {
+            bf16x8 v = zero8();
+            if (row0 + r < M)
+                v = *(const bf16x8*)&x[(long)(row0 + r) * H + col];
+            *(bf16x8*)&tile[r][col] = v;
+        }
+        __syncthreads();
+    } else
+#endif
     // ---- layer 0 from x: chunk c sits in xs buffer c & 1; the loads of
     // chunk c + 1 are issued ahead of chunk c's MFMAs and written after
     // them; the barrier that ends a chunk frees the buffer that the next
@@ -249,7 +284,7 @@ void FWD_WIDE_KERNEL(
 
     // ---- the H-wide layers, in place: the tile holds h_{l-1} (the h
     // store above only reads it, and so does the K loop)
-    for (int l = 1; l < nlayers; ++l) {
+    for (int l = l0; l < nlayers; ++l) {
         const gbf16* const w = (const gbf16*)L.w[l];
         load_bias(l);
 #if FWD_WIDE_DROP == 2
@@ -261,6 +296,7 @@ void FWD_WIDE_KERNEL(
         finish_layer(l);
     }
 
+#if FWD_WIDE_HEAD
     // ---- head: wave i < FM takes rows [16 i, +16) of the tile (whole
     // since the barrier inside finish_layer; nothing writes it again)
     // against W_head's rows, rows >= C as zeros; K in order, as
@@ -283,6 +319,7 @@ void FWD_WIDE_KERNEL(
         HEAD_FWD_EPILOGUE(1, hacc, b_head, probs, cvalid, lrow, kch, row_base,
                           M, C)
     }
+#endif
 }
 
 // This arm's launch.  rows / waves: 0 = the shipped choice (docs/KERNELS.md,
@@ -290,15 +327,22 @@ void FWD_WIDE_KERNEL(
 // with_chain_wide_arm's.  The arm under dropout takes its FwdChainDrop
 // block and refuses one that masks no layer of the launch, names a layer
 // past nlayers, carries a scale or threshold that no p in [0, 1) gives,
-// or whose last row is no 32-bit sample id.
+// or whose last row is no 32-bit sample id.  The stage arm takes `start`
+// in place of the head: 0 = by K0 (the tile start at K0 == H), 1 = the
+// streamed first layer, 2 = the tile start, refused unless K0 == H.
 bool FWD_WIDE_LAUNCH(const void* x, const void* const* w,
                      const void* const* b, void* const* h, int nlayers,
+#if FWD_WIDE_HEAD
                      const void* W_head, const void* b_head, void* probs,
                      int M, int K0, int H, int C, int rows, int waves,
+#else
+                     int M, int K0, int H, int rows, int waves, int start,
+#endif
 #if FWD_WIDE_DROP
                      const FwdChainDrop& D,
 #endif
                      hipStream_t st) {
+#if FWD_WIDE_HEAD
     if (M < 1 || M > INT32_MAX - 64 || (H != 128 && H != 512) || C < 1 ||
         C > 16 || nlayers < 1 || nlayers > SS_FWD_CHAIN_MAX || K0 < 8 ||
         K0 % 8 != 0)
@@ -306,6 +350,13 @@ bool FWD_WIDE_LAUNCH(const void* x, const void* const* w,
     if (!aligned16(x) || !aligned16(W_head) || !aligned16(b_head) ||
         !aligned16(probs))
         return false;
+#else
+    if (M < 1 || M > INT32_MAX - 64 || (H != 128 && H != 512) ||
+        nlayers < 1 || nlayers > SS_FWD_CHAIN_MAX || K0 < 8 || K0 % 8 != 0 ||
+        start < 0 || start > 2 || (start == 2 && K0 != H) || !aligned16(x))
+        return false;
+    const int tile0 = start == 2 || (start == 0 && K0 == H);
+#endif
 #if FWD_WIDE_DROP
     if (D.on == 0 || (D.on >> nlayers) != 0 ||
         (unsigned long)D.row_first +
@@ -334,8 +385,12 @@ bool FWD_WIDE_LAUNCH(const void* x, const void* const* w,
 #if FWD_WIDE_DROP
                            D,
 #endif
+#if FWD_WIDE_HEAD
                            (const __bf16*)W_head, (const __bf16*)b_head,
                            (__bf16*)probs, M, K0, C);
+#else
+                           M, K0, tile0);
+#endif
     };
     return H == 128 ? with_chain_wide_arm<128>(rows, waves, launch)
                     : with_chain_wide_arm<512>(rows, waves, launch);

@@ -319,6 +319,31 @@ bool ss_fwd_chain_wide_dropout(const void* x, const void* const* w,
                                int H, int C, int rows, int waves,
                                const FwdChainDrop& drop, hipStream_t stream);
 
+// ---- fwd_chain_wide_stage.hip / fwd_chain_wide_stage_drop.hip /
+// bwd_chain_wide_stage.hip
+// The stage arms of the wide chains, for a pipeline stage with no head:
+// the contract above without the head (H 128 or 512, 1..8 layers, M >= 1,
+// K0 >= 8 and K0 % 8 == 0, 16-byte-aligned pointers, a built arm, the last
+// layer's wt present exactly when dx is).  The forward ends with h of the
+// top layer.  start: 0 = by K0 (K0 == H: x is loaded into the tile and
+// layer 0 runs the in-place K loop; else the first layer streams x), 1 =
+// streamed, 2 = tile, false unless K0 == H.  The backward starts from
+// dout [M][H], the received gradient of the top layer's output.
+bool ss_fwd_chain_wide_stage(const void* x, const void* const* w,
+                             const void* const* b, void* const* h,
+                             int nlayers, int M, int K0, int H, int rows,
+                             int waves, int start, hipStream_t stream);
+bool ss_fwd_chain_wide_stage_dropout(const void* x, const void* const* w,
+                                     const void* const* b, void* const* h,
+                                     int nlayers, int M, int K0, int H,
+                                     int rows, int waves, int start,
+                                     const FwdChainDrop& drop,
+                                     hipStream_t stream);
+bool ss_bwd_chain_wide_stage(const void* dout, const void* const* h,
+                             const void* const* wt, void* const* dz,
+                             int nlayers, void* dx, int M, int H, int rows,
+                             int waves, float dz_scale, hipStream_t stream);
+
 // ---- fused_mlp.hip
 bool ss_fused_mlp_fwd(const void* x, const void* desc, int M, int in_dim,
                       int nhidden, int cout, void* out, hipStream_t stream);

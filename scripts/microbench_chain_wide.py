@@ -15,7 +15,12 @@ table gives the best, the median and the slowest round.  Needs a GPU.
               the same shapes with p = 0.2 on every ReLU layer: the
               per-layer path against fwd_chain_wide_dropout and
               bwd_chain_wide(dz_scale), both kernels and the training
-              step (profiles/r24_chain_wide_dropout.md)"""
+              step (profiles/r24_chain_wide_dropout.md)
+  python scripts/microbench_chain_wide.py stage [H M]
+              the stage arms, for a pipeline stage with no head: every
+              arm and both starts against the per-layer launches, p = 0
+              and 0.2, and the stage step with the wide chains off and on
+              (profiles/r25_chain_wide_stage.md); H M: that shape only"""
 import statistics
 import sys
 
@@ -134,8 +139,108 @@ def dropout_section():
     F.set_chain_wide_dropout(False)
 
 
+def stage_section(only=None):
+    """`stage [H M]`: the stage arms (csrc/fwd_chain_wide_stage.hip,
+    fwd_chain_wide_stage_drop.hip, bwd_chain_wide_stage.hip) per width and
+    batch, three ReLU layers, no head.  Forward: 3 x gemm_nt against every
+    arm, for a stage 0 (in_dims 784, streamed) and for a middle stage
+    (in_dims H) under both starts.  Backward from dout: 3 x relu_bwd +
+    gemm_nt against every arm, for a middle stage (three dgrads, dx out)
+    and a stage 0 (two).  The same under p = 0.2 on the shipped arm.  Then
+    the stage step (zero_grad, forward, backward with its wgrads) of a
+    stage-0 and a middle-stage model, F.set_chain_wide off against on."""
+    from shallowspeed_amd.models import MLP
+
+    p, seed, layers = 0.2, 0x1234567887654321, (0, 1, 2)
+    thr, scale = F.dropout_params(p)
+    k0, k1 = seed & 0xFFFFFFFF, seed >> 32
+    key = (seed, 7, layers, (p,) * N, 0, 1)
+    for H in F.CHAIN_WIDE_WIDTHS:
+        for M in (1024, 16384):
+            if only and (H, M) != only:
+                continue
+            xs = {IN0: rnd(M, IN0), H: rnd(M, H)}
+            ws = {k: [rnd(H, d, scale=d ** -0.5) for d in [k] + [H] * (N - 1)]
+                  for k in xs}
+            bs = [rnd(H, scale=0.1) for _ in range(N)]
+            dout = rnd(M, H, scale=1 / 64)
+            hs_top = F.fwd_chain_wide_stage(xs[H], ws[H], bs)[::-1]
+            hd_top = F.fwd_chain_wide_stage_dropout(xs[H], ws[H], bs,
+                                                    *key)[::-1]
+            w_ts = [w.t().contiguous() for w in ws[H][::-1]]  # top first
+
+            def fwd_layers(k, drop=False):
+                h = xs[k]
+                for l, w, b in zip(layers, ws[k], bs):
+                    h = e.gemm_nt_dropout(h, w, b, k0, k1, 7, l, 0, 1, thr,
+                                          scale, True) if drop \
+                        else e.gemm_nt(h, w, b, empty, True)
+
+            def bwd_layers(nw, s=1.0):
+                dh = dout
+                for l in range(N):
+                    dz = F.relu_bwd(dh, (hd_top if s != 1.0 else hs_top)[l],
+                                    scale=s)
+                    if l < nw:
+                        dh = e.gemm_nt(dz, w_ts[l], empty, empty, False)
+
+            print(f"stage H={H} M={M} layers={N}")
+            arms = {"fwd per layer in=784": lambda: fwd_layers(IN0),
+                    "fwd per layer in=H": lambda: fwd_layers(H),
+                    "bwd per layer 3 dgrads": lambda: bwd_layers(3),
+                    "bwd per layer 2 dgrads": lambda: bwd_layers(2)}
+            for arm in F.CHAIN_WIDE_ARMS[H]:
+                tag = " rows=%d waves=%d" % arm
+                arms["fwd stage in=784" + tag] = (
+                    lambda a=arm: F.fwd_chain_wide_stage(xs[IN0], ws[IN0], bs,
+                                                         *a))
+                for start, name in ((1, "streamed"), (2, "tile")):
+                    arms[f"fwd stage in=H {name}" + tag] = (
+                        lambda a=arm, s=start: F.fwd_chain_wide_stage(
+                            xs[H], ws[H], bs, *a, s))
+                for nw in (3, 2):
+                    arms[f"bwd stage {nw} dgrads" + tag] = (
+                        lambda a=arm, n=nw: F.bwd_chain_wide_stage(
+                            dout, hs_top, w_ts[:n], *a))
+            bench(arms)
+            print(f"stage dropout p={p} H={H} M={M} layers={N}")
+            bench({
+                "fwd per layer drop in=784": lambda: fwd_layers(IN0, True),
+                "fwd per layer drop in=H": lambda: fwd_layers(H, True),
+                "fwd stage drop in=784": lambda: F.fwd_chain_wide_stage_dropout(
+                    xs[IN0], ws[IN0], bs, *key),
+                "fwd stage drop in=H streamed": lambda:
+                    F.fwd_chain_wide_stage_dropout(xs[H], ws[H], bs, *key,
+                                                   0, 0, 1),
+                "fwd stage drop in=H tile": lambda:
+                    F.fwd_chain_wide_stage_dropout(xs[H], ws[H], bs, *key,
+                                                   0, 0, 2),
+                "bwd per layer scaled 3 dgrads": lambda: bwd_layers(3, scale),
+                "bwd stage dz_scale 3 dgrads": lambda: F.bwd_chain_wide_stage(
+                    dout, hd_top, w_ts, dz_scale=scale),
+            })
+            models = {"stage 0": MLP([IN0] + [H] * 4 + [C], 0, 2, M),
+                      "middle": MLP([H] * 8 + [C], 1, 3, M)}
+            steps = {}
+            for name, model in models.items():
+                model.materialize_device(dev)
+
+                def step(on, model=model, k=model.layers[0].in_dims):
+                    F.set_chain_wide(on)
+                    model.zero_grad()
+                    model.forward(xs[k], 0)
+                    model.backward(dout, 0)
+
+                steps[f"step {name}, SS_CHAIN_WIDE=0"] = lambda s=step: s(False)
+                steps[f"step {name}, SS_CHAIN_WIDE=1"] = lambda s=step: s(True)
+            bench(steps)
+
+
 if sys.argv[1:] == ["dropout"]:
     dropout_section()
+    sys.exit(0)
+if sys.argv[1:2] == ["stage"]:
+    stage_section(tuple(int(a) for a in sys.argv[2:4]) or None)
     sys.exit(0)
 
 for H in F.CHAIN_WIDE_WIDTHS:

@@ -736,7 +736,22 @@ class Sequential(Module):
             return None
         return pair[0].in_dims
 
-    def _fwd_wide_plan(self, rows=None):
+    def _wide_stage_width(self, rows=None):
+        """out_dims of the stage's last layer when the stage arms of the
+        wide chain kernels (F.fwd_chain_wide_stage /
+        F.bwd_chain_wide_stage) run up to it at `rows` micro-batch rows:
+        no head pair, a Linear of a width in F.CHAIN_WIDE_WIDTHS, and
+        F.chain_wide_planned.  Else None."""
+        if self._head_pair() is not None or not self.layers:
+            return None
+        top = self.layers[-1]
+        if type(top) is not Linear \
+                or top.out_dims not in F.CHAIN_WIDE_WIDTHS \
+                or not F.chain_wide_planned(top.out_dims, rows):
+            return None
+        return top.out_dims
+
+    def _fwd_wide_plan(self, rows=None, stage=False):
         """_fwd_chain_plan at width H = 128 or 512 (the head Linear's
         in_dims), for F.fwd_chain_wide: the run of Linear(activation=
         "relu") layers with out_dims == H right under the fused head, at
@@ -748,12 +763,18 @@ class Sequential(Module):
         model's, for F.fwd_chain_wide_dropout in training mode and
         F.fwd_chain_wide in eval mode.  Consulted only where
         _fwd_chain_plan() is None; width 256 is that plan's.  rows: the
-        micro-batch rows, where the caller knows them."""
-        width = self._wide_head_width(rows)
+        micro-batch rows, where the caller knows them.
+
+        stage (for _fwd_wide_stage_plan): the run starts at the stage's
+        last layer, whose out_dims is the width, and no head is asked
+        for."""
+        width = self._wide_stage_width(rows) if stage \
+            else self._wide_head_width(rows)
         if width is None:
             return None
         plan = []
-        for i in self._chain_run(width=width):
+        top = len(self.layers) - 1 if stage else None
+        for i in self._chain_run(top, width=width):
             layer = self.layers[i]
             streamed = layer.in_dims != width
             if streamed and (layer.in_dims < 8 or layer.in_dims % 8 != 0):
@@ -766,19 +787,33 @@ class Sequential(Module):
                 break
         return plan[::-1] or None
 
-    def _bwd_wide_plan(self, mubatch_rows: int = 1):
+    def _fwd_wide_stage_plan(self, rows=None):
+        """_fwd_wide_plan for a stage with no head pair (every pipeline
+        stage but the last), for F.fwd_chain_wide_stage: the run of
+        Linear(activation="relu") layers of width H = 128 or 512 that
+        ends at the stage's last layer, by the same rules.  None whenever
+        there is a head pair.  Consulted only where _fwd_stage_plan() is
+        None."""
+        return self._fwd_wide_plan(rows, stage=True)
+
+    def _bwd_wide_plan(self, mubatch_rows: int = 1, stage=False):
         """_bwd_chain_plan at width H = 128 or 512, for F.bwd_chain_wide:
         (layer index, dgrad_in_chain), top layer first.  A layer's dgrad
         is in the chain when in_dims == H and its dx is needed; the
         chain ends with the first layer whose dgrad is not (that layer
         still gets its dz from the kernel).  None with dropout on a
         planned layer unless F.chain_wide_dropout_enabled().  Consulted
-        only where _bwd_chain_plan() is None."""
-        width = self._wide_head_width(mubatch_rows)
+        only where _bwd_chain_plan() is None.
+
+        stage (for _bwd_wide_stage_plan): the run starts at the stage's
+        last layer and no head is asked for."""
+        width = self._wide_stage_width(mubatch_rows) if stage \
+            else self._wide_head_width(mubatch_rows)
         if width is None or mubatch_rows < 1:
             return None
         plan = []
-        for i in self._chain_run(width=width):
+        top = len(self.layers) - 1 if stage else None
+        for i in self._chain_run(top, width=width):
             layer = self.layers[i]
             if layer.dropout > 0.0 and not F.chain_wide_dropout_enabled():
                 return None
@@ -795,6 +830,13 @@ class Sequential(Module):
             return None
         return plan or None
 
+    def _bwd_wide_stage_plan(self, mubatch_rows: int = 1):
+        """_bwd_wide_plan for a stage with no head pair, for
+        F.bwd_chain_wide_stage on the received gradient.  None whenever
+        there is a head pair.  Consulted only where _bwd_stage_plan() is
+        None."""
+        return self._bwd_wide_plan(mubatch_rows, stage=True)
+
     def _forward_chain(self, plan, lin, head, x, mubatch_id, launch=None,
                        drop=False):
         """Forward of the planned ReLU layers and the head pair through
@@ -804,7 +846,9 @@ class Sequential(Module):
         = None (a stage plan): ONE F.fwd_chain_stage launch, which never
         takes a deferred zero_grad along; returns the top layer's
         output.  launch (a wide plan): F.fwd_chain_wide in place of
-        F.fwd_chain, which takes no deferred zero_grad along either.
+        F.fwd_chain (F.fwd_chain_wide_stage in place of
+        F.fwd_chain_stage), which takes no deferred zero_grad along
+        either.
         drop (a _fwd_drop_plan, or a wide plan of a model with dropout):
         where a planned layer drops out in this forward (training mode),
         F.fwd_chain_dropout / F.fwd_chain_stage_dropout /
@@ -823,8 +867,12 @@ class Sequential(Module):
         if lin is None:
             ws = [l.weight.compute() for l in chain]
             bs = [l.bias.compute() for l in chain]
-            hs = F.fwd_chain_stage_dropout(x, ws, bs, *dargs) if dargs \
-                else F.fwd_chain_stage(x, ws, bs)
+            if launch:
+                hs = F.fwd_chain_wide_stage_dropout(x, ws, bs, *dargs) \
+                    if dargs else launch(x, ws, bs)
+            else:
+                hs = F.fwd_chain_stage_dropout(x, ws, bs, *dargs) if dargs \
+                    else F.fwd_chain_stage(x, ws, bs)
             if hs is None:
                 return None
             for layer, h in zip(chain, hs):
@@ -873,6 +921,10 @@ class Sequential(Module):
             if plan is None and pair:
                 plan = self._fwd_wide_plan(inputs.shape[0])
                 wide = F.fwd_chain_wide if plan else None
+                drop = plan is not None and self._has_dropout
+            elif plan is None:
+                plan = self._fwd_wide_stage_plan(inputs.shape[0])
+                wide = F.fwd_chain_wide_stage if plan else None
                 drop = plan is not None and self._has_dropout
             if plan is None:
                 plan = self._fwd_drop_plan()
@@ -1031,14 +1083,15 @@ class Sequential(Module):
         lin = head = None (a stage plan): `target` is the gradient the
         stage received, and the launch is ONE F.bwd_chain_stage on it;
         the wgrads follow in the same way.  launch (a wide plan):
-        F.bwd_chain_wide in place of F.bwd_chain, with the same dz_scale;
+        F.bwd_chain_wide in place of F.bwd_chain (F.bwd_chain_wide_stage
+        in place of F.bwd_chain_stage), with the same dz_scale;
         everything after the launch is the same."""
         chain = [self.layers[i] for i, _ in plan]
         hs = [l._cache.get(("y", mubatch_id)) for l in chain]
         if lin is None:
             if any(h is None for h in hs):
                 return False, None
-            res = F.bwd_chain_stage(
+            res = (launch or F.bwd_chain_stage)(
                 target, hs, [l.weight.compute_t()
                              for l, (_, dg) in zip(chain, plan) if dg],
                 dz_scale=chain[0].dz_scale())
@@ -1139,6 +1192,9 @@ class Sequential(Module):
             if plan is None and pair:
                 plan = self._bwd_wide_plan(dout.shape[0])
                 wide = F.bwd_chain_wide if plan else None
+            elif plan is None:
+                plan = self._bwd_wide_stage_plan(dout.shape[0])
+                wide = F.bwd_chain_wide_stage if plan else None
         if plan:
             ok, dx = self._backward_chain(plan, *(pair or (None, None)), d,
                                           mubatch_id, wide)

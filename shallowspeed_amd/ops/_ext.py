@@ -97,6 +97,9 @@ def build_ext(verbose=True):
         os.path.join(src_dir, "fwd_chain_wide_drop.hip"),
         os.path.join(src_dir, "bwd_chain_wide.hip"),
         os.path.join(src_dir, "bwd_chain_wide_mse.hip"),
+        os.path.join(src_dir, "fwd_chain_wide_stage.hip"),
+        os.path.join(src_dir, "fwd_chain_wide_stage_drop.hip"),
+        os.path.join(src_dir, "bwd_chain_wide_stage.hip"),
     ]
     mod = load(
         name=_EXT_NAME,

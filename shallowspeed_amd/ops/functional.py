@@ -258,8 +258,10 @@ def set_chain_wide(flag: bool):
     under the fused head are 128 or 512 wide as the chain kernels of
     csrc/fwd_chain_wide.hip and csrc/bwd_chain_wide.hip (see
     fwd_chain_wide / bwd_chain_wide; width 256 keeps fwd_chain /
-    bwd_chain).  Every h_l, probs, dz and dx keeps its bits.  One switch
-    for both: True plans them at every batch, False never;
+    bwd_chain), and those of a pipeline stage with no head that ends in
+    such layers as their stage arms (fwd_chain_wide_stage /
+    bwd_chain_wide_stage).  Every h_l, probs, dz and dx keeps its bits.
+    One switch for all of them: True plans them at every batch, False never;
     SS_CHAIN_WIDE=1 / 0 (read once) does the same.  Left alone, they are
     planned where they were measured to win: chain_wide_planned."""
     global _CHAIN_WIDE
@@ -287,7 +289,10 @@ def chain_wide_enabled() -> bool:
 # times its run-to-run spread (profiles/r20_chain_wide.md).  H = 512 wins
 # at 16384 rows (0.229 against 0.284 ms) and loses at 1024 (0.147 against
 # 0.136); H = 128 wins at 1024 and loses at 16384, and stays unplanned
-# until the batch at which it turns is measured.
+# until the batch at which it turns is measured.  The stage arms, for a
+# pipeline stage with no head, follow the same table: their step at
+# H = 512, 16384 rows wins by 50 µs and more against a spread under 1 µs,
+# and loses at 1024 rows (profiles/r25_chain_wide_stage.md).
 CHAIN_WIDE_MIN_ROWS = {512: 16384}
 
 
@@ -1107,6 +1112,69 @@ def bwd_chain_wide(probs, target, w_head_t, global_batch, hs, w_ts, rows=0,
         return None
     n = len(hs)
     return out[0], out[1:1 + n], (out[1 + n] if len(w_ts) == n else None)
+
+
+def fwd_chain_wide_stage(x, ws, bs, rows=0, waves=0, start=0):
+    """fwd_chain_stage at hidden width H = 128 or 512 (GPU only,
+    csrc/fwd_chain_wide_stage.hip): the ReLU layers of a pipeline stage
+    that has no head in one kernel; H is ws[0]'s out_dims.
+
+      h_l = relu(h_{l-1} @ W_l^T + b_l)
+
+    ws / bs / x and rows / waves as fwd_chain_wide.  start: how layer 0
+    begins.  0 = by x's width: at H (a middle stage) x is loaded into the
+    kernel's tile and layer 0 runs the K loop of the later layers; at any
+    other multiple of 8 the first layer streams x.  1 = streamed, 2 =
+    tile (refused unless x is H wide); same bits either way.
+
+    Returns [h_l, ...] (the last one is what the stage sends on), each
+    bit-identical to linear_fwd(relu) -> ..., or None, with nothing
+    launched, outside the kernel's contract (fwd_chain_wide's without
+    the head)."""
+    if not _is_gpu(x):
+        return None
+    out = _ext_for(x).fwd_chain_wide_stage(x, list(ws), list(bs), int(rows),
+                                           int(waves), int(start))
+    return out or None
+
+
+def fwd_chain_wide_stage_dropout(x, ws, bs, seed, step, layers, ps, row_first,
+                                 row_stride, rows=0, waves=0, start=0):
+    """fwd_chain_wide_stage under dropout (GPU only,
+    csrc/fwd_chain_wide_stage_drop.hip): arguments as
+    fwd_chain_wide_dropout without the head.  Returns [h_l, ...] (the
+    last one, dropped out, is what the stage sends on), each bit-identical
+    to linear_fwd_dropout -> ..., or None, with nothing launched, outside
+    the contract."""
+    if not _is_gpu(x):
+        return None
+    drop = _chain_drop_args(x, seed, step, layers, ps, row_first, row_stride)
+    if drop is None:
+        return None
+    out = _ext_for(x).fwd_chain_wide_stage_dropout(
+        x, list(ws), list(bs), *drop, int(rows), int(waves), int(start))
+    return out or None
+
+
+def bwd_chain_wide_stage(dout, hs, w_ts, rows=0, waves=0, dz_scale=1.0):
+    """bwd_chain_stage at hidden width H = 128 or 512 (GPU only,
+    csrc/bwd_chain_wide_stage.hip): the ReLU-layer data gradients of a
+    pipeline stage that has no head in one kernel, from dout (M, H), the
+    gradient received for the top layer's output.  hs / w_ts / dz_scale
+    as bwd_chain_wide.
+
+    Returns ([dz_l, ...], dx or None), each bit-identical to relu_bwd ->
+    linear_dgrad -> ..., or None, with nothing launched, outside the
+    kernel's contract."""
+    if not _is_gpu(dout):
+        return None
+    out = _ext_for(dout).bwd_chain_wide_stage(dout, list(hs), list(w_ts),
+                                              int(rows), int(waves),
+                                              float(dz_scale))
+    if not out:
+        return None
+    n = len(hs)
+    return out[:n], (out[n] if len(w_ts) == n else None)
 
 
 def xent_loss(probs, target, global_batch, eps=1e-9):
